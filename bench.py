@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: AnymalTerrain VecTask.step throughput (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs 4096] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs 4096] [--dump-outputs DIR]
+    python bench.py --full [--steps K] [--warmup W] [--no-cpu-baseline] [--ppo-epochs E] [--other-steps S]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step
+when --dump-outputs is given, and prints the result line (headline fields only; the legs below
+are null).  --full adds the legs listed below to the same line.
 
 One "step" = one ``VecTask.step(actions)`` of AnymalTerrain (default config:
 terrainType plane, 4096 envs per GPU, seed 42 + rank) with synthetic uniform
@@ -12,8 +17,12 @@ the post-physics tail, resets, observation noise.  Envs shard across ranks with
 no data-path collective (weak scaling); the only collectives are the barrier and
 the max-over-ranks of the timed region.
 
-The rank-0 JSON line carries:
-  roofline     -- the fused physics kernel (gs_sim_pd_step): SURVEY.md 8(d)'s algorithmic HBM
+--dump-outputs DIR writes what the last timed VecTask.step returned, as float32 DIR/<name>.npy:
+obs (N x 188), rew (N), reset (N, 0/1), time_outs (N, 0/1).  Seeds, env count and action pool are
+fixed by the arguments, so two builds run with the same arguments can be compared array for array.
+
+With --full the rank-0 JSON line also carries:
+  roofline    -- the fused physics kernel (gs_sim_pd_step): SURVEY.md 8(d)'s algorithmic HBM
                   bytes of the env step per launch / its average HIP-event duration on the launch
                   stream (the kernel-scoped bytes beside it);
   cpu_baseline -- the product's CPU pipeline (sim_device=cpu pipeline=cpu: libgymsim's host
@@ -73,6 +82,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--num-envs", type=int, default=4096, help="envs per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, CPU-baseline, PPO and other-config legs (the options below tune them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall budget of the CPU baseline sample")
     ap.add_argument("--kernel-launches", type=int, default=50, help="launches timed for the roofline figure")
@@ -300,6 +313,84 @@ def other_config_leg(task, desc, overrides, num_envs, steps, warmup, device, ran
     return out
 
 
+def dump_outputs(out_dir, result, rank, world):
+    """What a caller of the timed path received from its last VecTask.step, as float32 <name>.npy
+    (<name>.rank<r>.npy on the ranks after the first): obs, rew, reset and time_outs (the bools as 0/1).
+    4096 envs x 188 obs is 3.1 MB in all."""
+    import numpy as np
+    obs, rew, reset, extras = result
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, t in (("obs", obs["obs"]), ("rew", rew), ("reset", reset), ("time_outs", extras["time_outs"])):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.detach().to("cpu").numpy().astype(np.float32))
+
+
+def physics_kernel_ms(env, step, launches, device):
+    """Average duration of the fused physics launch: HIP events on the launch stream around each launch of
+    `launches` more VecTask.step calls (same workload as the timed region: the tail's resets keep the state
+    mix, so self-contacts and contact counts are the bench's own)."""
+    import torch
+    stream = torch.cuda.current_stream(device)
+    evs = []
+    inner = env.fused_physics_step
+
+    def timed_launch(actions):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        inner(actions)
+        e1.record(stream)
+        evs.append((e0, e1))
+
+    env.fused_physics_step = timed_launch
+    for _ in range(launches):
+        step()
+    env.fused_physics_step = inner
+    torch.cuda.synchronize()
+    assert len(evs) == launches, "the fused physics launch did not run once per step"
+    return sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+
+
+def roofline_report(kernel_ms, variant, N):
+    """Roofline of the dominant kernel.  Basis: SURVEY.md 8(d)'s step-scoped algorithmic bytes (2,434 B per env
+    step) per launch; the kernel-scoped bytes (what gs_sim_pd_step alone moves) beside it; measured traffic and
+    counted FP32 VALU FLOPs (SURVEY.md 8d "report both") from the counter summaries under profiles/ when they
+    were taken at this env count."""
+    kernel_name = {1: "k_pd_step<Topo_anymal_c>", 2: "k_pd_step_team<Topo_anymal_c>"}.get(variant, str(variant))
+    bytes_per_launch = STEP_BYTES_PER_ENV * N
+    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
+    kbytes_per_launch = physics_kernel_bytes_per_env() * N
+    kachieved = kbytes_per_launch / (kernel_ms * 1e-3) / 1e9
+    traffic, traffic_note = None, None
+    pmc = os.path.join(ROOT, "profiles", "pmc_pd_step.json")
+    if os.path.exists(pmc):
+        with open(pmc) as f:
+            d = json.load(f)
+        if d.get("num_envs") == N:
+            traffic = d.get("hbm_bytes_per_launch")
+            traffic_note = d.get("note")
+    valu = None
+    vj = os.path.join(ROOT, "profiles", "valu_pd_step.json")
+    if os.path.exists(vj):
+        with open(vj) as f:
+            d = json.load(f)
+        if d.get("num_envs") == N:
+            fl = d["fp32_flops_per_launch"]
+            ach = fl / (kernel_ms * 1e-3) / 1e12
+            valu = {"bound": "valu", "achieved": ach, "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": ach / FP32_VECTOR_PEAK_TFLOPS, "flops_per_launch": fl,
+                    "flops_per_env_step": d["fp32_flops_per_env_step"],
+                    "valu_busy_frac": d["busy_frac_valu"], "wait_frac": d["wait_frac"]}
+    return {"bound": "hbm", "kernel": f"gs_sim_pd_step ({kernel_name})",
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_note": traffic_note, "kernel_ms": kernel_ms,
+            "bytes_per_launch": bytes_per_launch,
+            "basis": f"SURVEY.md 8(d): {STEP_BYTES_PER_ENV} B per env step x {N} envs per launch",
+            "kernel_scoped": {"bytes_per_launch": kbytes_per_launch, "achieved": kachieved,
+                              "frac": kachieved / HBM_PEAK_GBS,
+                              "basis": "gs_sim_pd_step's own reads + writes, DESIGN.md section 5"},
+            "valu": valu}
+
+
 def main():
     # the driver reads ONE JSON line from rank 0's stdout: every other print (set_seed, rank banners,
     # the task layer) goes to stderr
@@ -364,81 +455,37 @@ def _main():
     n_batches = max(1, min(args.steps + args.warmup, 1024))
     pool = torch.empty((n_batches, N, A), device=device).uniform_(-1.0, 1.0, generator=gen)
     it = [0]
+    last = [None]  # what the most recent VecTask.step returned: (obs dict, rew, reset, extras)
 
     def step():
-        env.step(pool[it[0] % n_batches])
+        last[0] = env.step(pool[it[0] % n_batches])
         it[0] += 1
 
     elapsed = timed_region(step, args.steps, args.warmup, world, sync=torch.cuda.synchronize)
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, last[0], rank, world)
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream around each fused physics launch
-    # of `kernel_launches` more VecTask.step calls (same workload as the timed region: the tail's resets keep
-    # the state mix, so self-contacts and contact counts are the bench's own)
-    stream = torch.cuda.current_stream(device)
-    evs = []
-    inner = env.fused_physics_step
-
-    def timed_launch(actions):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        inner(actions)
-        e1.record(stream)
-        evs.append((e0, e1))
-
-    env.fused_physics_step = timed_launch
-    for _ in range(args.kernel_launches):
-        step()
-    env.fused_physics_step = inner
-    torch.cuda.synchronize()
-    assert len(evs) == args.kernel_launches, "the fused physics launch did not run once per step"
-    kernel_ms = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
     variant = env.gym.amd_kernel_variant(env.sim)
-    kernel_name = {1: "k_pd_step<Topo_anymal_c>", 2: "k_pd_step_team<Topo_anymal_c>"}.get(variant, str(variant))
     solver_type = int(env.sim.cparams.solver_type)
     solver = ("TGS" if solver_type == 1 and variant == 2 else "PGS") + f" (physx.solver_type {solver_type}, cfg/config.yaml:31)"
-    # roofline basis: SURVEY.md 8(d)'s step-scoped algorithmic bytes (2,434 B per env step) per launch of
-    # the dominant kernel; the kernel-scoped bytes (what gs_sim_pd_step alone moves) beside it
-    bytes_per_launch = STEP_BYTES_PER_ENV * N
-    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
-    kbytes_per_launch = physics_kernel_bytes_per_env() * N
-    kachieved = kbytes_per_launch / (kernel_ms * 1e-3) / 1e9
 
-    ppo = None
-    if args.ppo_epochs > 0:
-        ppo = ppo_leg(env, device, rank, world, args.ppo_epochs)
-    others = []
-    if args.other_steps > 0:
-        del env
-        for task, desc, ov, with_ppo in OTHER_CONFIGS:
-            if task not in args.others.split(","):
-                continue
-            others.append(other_config_leg(task, desc, ov, args.num_envs, args.other_steps, 20, device, rank, world,
-                                           ppo_epochs=min(args.ppo_epochs, 2) if with_ppo else 0))
+    kernel_ms, ppo, others = None, None, []
+    if args.full:
+        kernel_ms = physics_kernel_ms(env, step, args.kernel_launches, device)
+        if args.ppo_epochs > 0:
+            ppo = ppo_leg(env, device, rank, world, args.ppo_epochs)
+        if args.other_steps > 0:
+            del env
+            for task, desc, ov, with_ppo in OTHER_CONFIGS:
+                if task not in args.others.split(","):
+                    continue
+                others.append(other_config_leg(task, desc, ov, args.num_envs, args.other_steps, 20, device, rank,
+                                               world, ppo_epochs=min(args.ppo_epochs, 2) if with_ppo else 0))
 
     if rank == 0:
-        traffic, traffic_note = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_pd_step.json")
-        if os.path.exists(pmc):
-            with open(pmc) as f:
-                d = json.load(f)
-            if d.get("num_envs") == N:
-                traffic = d.get("hbm_bytes_per_launch")
-                traffic_note = d.get("note")
-        # secondary roofline (SURVEY.md 8d "report both"): counted FP32 VALU FLOPs of the same kernel
-        valu = None
-        vj = os.path.join(ROOT, "profiles", "valu_pd_step.json")
-        if os.path.exists(vj):
-            with open(vj) as f:
-                d = json.load(f)
-            if d.get("num_envs") == N:
-                fl = d["fp32_flops_per_launch"]
-                ach = fl / (kernel_ms * 1e-3) / 1e12
-                valu = {"bound": "valu", "achieved": ach, "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": ach / FP32_VECTOR_PEAK_TFLOPS, "flops_per_launch": fl,
-                        "flops_per_env_step": d["fp32_flops_per_env_step"],
-                        "valu_busy_frac": d["busy_frac_valu"], "wait_frac": d["wait_frac"]}
+        roofline = roofline_report(kernel_ms, variant, N) if args.full else None
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(N, args.cpu_seconds)
         total_env_steps = N * world * args.steps
         line = {
@@ -458,15 +505,7 @@ def _main():
                                    "5 physics substeps/step, obs noise on",
                        "num_envs_per_gpu": N, "global_num_envs": N * world, "parallelism": f"dp{world}",
                        "solver": solver},
-            "roofline": {"bound": "hbm", "kernel": f"gs_sim_pd_step ({kernel_name})",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_note": traffic_note, "kernel_ms": kernel_ms,
-                         "bytes_per_launch": bytes_per_launch,
-                         "basis": f"SURVEY.md 8(d): {STEP_BYTES_PER_ENV} B per env step x {N} envs per launch",
-                         "kernel_scoped": {"bytes_per_launch": kbytes_per_launch, "achieved": kachieved,
-                                           "frac": kachieved / HBM_PEAK_GBS,
-                                           "basis": "gs_sim_pd_step's own reads + writes, DESIGN.md section 5"},
-                         "valu": valu},
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "ppo": ppo,
             "other_configs": others,

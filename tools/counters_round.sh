@@ -12,7 +12,7 @@ ROOT=$PWD
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --ppo-epochs 0 --other-steps 10"
+BENCH="python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --ppo-epochs 0 --other-steps 10"
 timeout -k 10 120 $ROOT/tools/hbm_calib > $OUT/calib_bytes.json || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/calib_$c -o run -- \

@@ -4,7 +4,7 @@ import json, os, subprocess, sys
 for spec in sys.argv[1:]:
     lib, sc = spec.split(":")
     env = dict(os.environ, GS_LIBGYMSIM=lib, GS_SELF_COLLIDE=sc)
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--ppo-epochs", "0",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--ppo-epochs", "0",
                           "--other-steps", "20"], env=env, capture_output=True, text=True, timeout=500)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])

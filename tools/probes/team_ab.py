@@ -4,7 +4,7 @@ import json, os, subprocess, sys
 for rep in range(2):
     for lib in sys.argv[1:]:
         env = dict(os.environ, GS_LIBGYMSIM=lib)
-        out = subprocess.run([sys.executable, "bench.py", "--steps", "500", "--warmup", "50", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "500", "--warmup", "50", "--no-cpu-baseline",
                               "--ppo-epochs", "0", "--other-steps", "0"], env=env, capture_output=True, text=True, timeout=500)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -17,5 +17,5 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU" \
            "SQ_INSTS_VALU_FLOPS_FP32 SQ_INSTS_VALU_FLOPS_FP32_TRANS SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/sq_$i -o run -- \
-    python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/sq_$i.log 2>&1 || exit 1
+    python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/sq_$i.log 2>&1 || exit 1
 done

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 cd /tmp
 for V in default "$@"; do
   if [ "$V" = default ]; then export GS_LIBGYMSIM=libgymsim.so; else export GS_LIBGYMSIM=libgymsim_$V.so; fi
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$V -o run -- python3 $ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline --ppo-epochs 0 --other-steps 100 > $OUT/$V.json 2> $OUT/$V.err || exit 1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$V -o run -- python3 $ROOT/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --ppo-epochs 0 --other-steps 100 > $OUT/$V.json 2> $OUT/$V.err || exit 1
   rm -f $OUT/$V/*kernel_trace.csv
   echo "== $V" >> $OUT/summary.txt
   grep -h "_team<" $OUT/$V/run_kernel_stats.csv | cut -d, -f1-4 | cut -c1-40,110-220 >> $OUT/summary.txt

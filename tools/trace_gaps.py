@@ -1,5 +1,5 @@
 """GPU busy time and idle gaps per env step from a rocprofv3 kernel trace (headline bench steps and the last PPO
-rollout steps of a `bench.py ... --ppo-epochs K` run):
+rollout steps of a `bench.py --full ... --ppo-epochs K` run):
     python tools/trace_gaps.py gpurun_out/<tag>/trace/run_kernel_trace.csv [--steps 20]
 Per step: wall (pd_step start to the next pd_step start), busy (sum of kernel durations), and the mean gap before
 each kernel kind."""
