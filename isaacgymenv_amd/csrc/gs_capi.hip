@@ -10,6 +10,7 @@
 // sim_device=cpu pipeline): same entry points, caller-owned HOST buffers, the solver
 // runs on a thread pool inside the call, `stream` is ignored, no HIP call is made.
 #include <cmath>
+#include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
@@ -163,6 +164,11 @@ gs_sim* gs_sim_create(int device, const gs_sim_params* p) {
   s->dp.any_limits = 0;
   s->dp.has_ground = 0;
   s->dp.ground_mu = 1.f;
+  // A/B switch of the lane-team kernels' envs per wave, read once here; unset (or any other value): the default
+  if (const char* v = std::getenv("GS_TEAM_ENVS_PER_WAVE")) {
+    const int w = std::atoi(v);
+    s->dp.team_epw = w == 16 || w == 8 || w == 4 ? w : 0;
+  }
   return s;
 }
 

@@ -93,6 +93,9 @@ struct DevParams {
   const struct GenTopo* gen;
   const struct DevLinks* gen_links;
   int gen_nd, gen_nr;
+  // lane-team kernels: envs per wave of a launch, 16 / 8 / 4 (GS_TEAM_ENVS_PER_WAVE at gs_sim_create); 0 = the
+  // kernel's own default for the scene (gs_team.hip team_epw)
+  int team_epw;
 };
 #define GS_DOFP_FIELDS 6
 

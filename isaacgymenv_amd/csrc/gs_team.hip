@@ -14,7 +14,8 @@
 //     the row itself read from lane c's LDS column (16 teams read 16 addresses, 4-way broadcast).
 // Rows are processed in the oracle's global order (root candidates, then chain 0, 1, ...), so
 // the iterates are the same projected Gauss-Seidel sequence, only the rounding order of the base
-// sums differs.  4096 envs -> 256 waves; per-chain model constants are staged in LDS.
+// sums differs.  4096 envs -> 256 workgroups of 16 envs, each 1, 2 or 4 waves (WaveForm); per-chain model constants
+// are staged in LDS.
 #include <type_traits>
 
 #include "gs_internal.h"
@@ -147,6 +148,42 @@ static_assert(kTeamBlock % 4 == 0 && kTeamBlock <= GS_WAVE, "a workgroup holds w
 // different slots of one column land in 4 different banks (and a narrow workgroup's rows stay small
 // enough for several workgroups per CU)
 constexpr int RW = kTeamBlock + 1;
+
+// Envs (teams) per wave, EPW in {16, 8, 4}: a launch-time property of the team kernels.  A workgroup
+// always holds kTeamBlock / 4 = 16 envs and the LDS tables above keep one layout; with EPW < 16 it runs 16 / EPW
+// waves, each on its own SIMD, and a wave's lanes 0 .. 4 EPW - 1 own consecutive columns of the tables (the other
+// lanes leave after the staging barrier).  A wave executes a contact slot when ANY of its envs has it active, so
+// fewer envs per wave execute fewer slots.  The waves of a workgroup share only the tables staged before that one
+// barrier (read-only afterwards); everything a substep writes is in the wave's own columns or its own slice of the
+// shape table, so past the barrier the waves are never coupled: the ordering points are wave-local (team_sync).
+template <int EPW>
+struct WaveForm {
+  static_assert(EPW == 16 || EPW == 8 || EPW == 4, "envs per wave");
+  static constexpr bool kWhole = EPW * 4 >= kTeamBlock;  // the one-wave workgroup (also every GS_TEAM_BLOCK < 64 build)
+  static constexpr int TEAMS = kWhole ? kTeamBlock / 4 : EPW;  // teams of a wave
+  static constexpr int LANES = 4 * TEAMS;                      // live lanes of a wave
+  static constexpr int WAVES = kTeamBlock / LANES;             // waves of a workgroup
+  static constexpr int THREADS = kWhole ? kTeamBlock : GS_WAVE * WAVES;
+};
+// this thread's column of the workgroup's per-lane LDS tables (rows, the stash; column >> 2: its team's)
+template <int EPW>
+__device__ __forceinline__ int team_column() {
+  if constexpr (WaveForm<EPW>::kWhole) return threadIdx.x;
+  else return (threadIdx.x / GS_WAVE) * WaveForm<EPW>::LANES + (threadIdx.x & (GS_WAVE - 1));
+}
+// Orders this wave's LDS (and global) writes before its other lanes' reads.  The one-wave workgroup keeps
+// __syncthreads() (its barrier folds away); a multi-wave workgroup must not couple its waves -- a wave whose envs
+// are past N has left, and the waves are not in phase -- so there it is the same fences around a wave barrier.
+template <int EPW>
+__device__ __forceinline__ void team_sync() {
+  if constexpr (WaveForm<EPW>::kWhole) {
+    __syncthreads();
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+}
 
 // LDS contact records, layout [slot][lane]: chain candidates in the owner lane's column, then root
 // candidates (replicated, every lane its own column).  A record holds everything a lane needs
@@ -563,17 +600,17 @@ __device__ __forceinline__ unsigned long long quad_or64(unsigned long long m) {
 // The replicated narrowphase (the round-4 path, now the fallback of team_self_contacts when a lane holds more
 // contacts than it stages): every lane publishes its chain's shapes' full poses (lane 0 also the root's) to the
 // team's LDS table, and each lane of a team runs gs_pairs.h self_contacts over the team's near pairs.
-template <class T>
+template <class T, int EPW>
 __device__ __forceinline__ int team_narrow_replicated(const DevModel* __restrict__ M, const DevParams& P,
                                                    const float* __restrict__ mu_g, int N, int e, int lc,
                                                    const float (&R0)[9], const float (&R)[T::T_CL][9],
                                                    const float (&X)[T::T_CL][3], unsigned long long near,
                                                    float* __restrict__ shw_tab, const float* __restrict__ sct,
                                                    float* __restrict__ pool) {
-  constexpr int TPW = kTeamsPerBlock;
-  const int team = threadIdx.x >> 2;
+  constexpr int TPW = WaveForm<EPW>::TEAMS;  // (shw_tab: the wave's slice of the table)
+  const int team = (threadIdx.x & (GS_WAVE - 1)) >> 2;
   float* tab = shw_tab + team;
-  __syncthreads();  // the staging above may still be read
+  team_sync<EPW>();  // the staging above may still be read
   // full shape poses for the narrowphase: R (9), centre (3), bounding-sphere centre (3)
 #pragma unroll
   for (int j = 0; j < T::T_SPC; ++j) {
@@ -609,7 +646,7 @@ __device__ __forceinline__ int team_narrow_replicated(const DevModel* __restrict
       }
     }
   }
-  __syncthreads();
+  team_sync<EPW>();
   // the team's near pairs (team-uniform mask) -> the narrowphase of those pairs, replicated in the team's lanes
   const unsigned long long tmask = quad_or64(near);
   int cnt = 0;
@@ -626,13 +663,15 @@ __device__ __forceinline__ int team_narrow_replicated(const DevModel* __restrict
 // LDS table and runs the narrowphase, replicated in each lane of the teams concerned (gs_pairs.h self_contacts:
 // the pair order and rules of the one-env-per-lane solver and the oracle).  Returns the team's self-contact count
 // (the pool in the lane's own column).
-template <class T>
+template <class T, int EPW>
 __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M, const float* __restrict__ cm,
                                                   const DevParams& P, const float* __restrict__ mu_g, int N, int e,
                                                   int lc, const float (&R0)[9], const float (&R)[T::T_CL][9],
                                                   const float (&X)[T::T_CL][3], float* __restrict__ shw_tab,
                                                   const float* __restrict__ sct, float* __restrict__ pool) {
-  constexpr int TPW = kTeamsPerBlock, LN = T::T_LANES, SPC = T::T_SPC, RSH = T::T_RS;
+  // (TPW teams and WL lanes of this wave; shw_tab is the wave's slice of the workgroup's table)
+  constexpr int TPW = WaveForm<EPW>::TEAMS, WL = WaveForm<EPW>::kWhole ? 64 : WaveForm<EPW>::LANES;
+  constexpr int LN = T::T_LANES, SPC = T::T_SPC, RSH = T::T_RS;
   using C = CM<T>;
   // (conservative by a hair: the narrowphase recomputes the distance in another association order)
   const float off = P.contact_offset * 1.001f + 1e-5f;
@@ -739,7 +778,7 @@ __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M
 #endif
   if constexpr (!team_closed_form<T>()) {
     // GJK pairs: the replicated narrowphase (every pair kind of gs_pairs.h self_pair)
-    return team_narrow_replicated<T>(M, P, mu_g, N, e, lc, R0, R, X, near, shw_tab, sct, pool);
+    return team_narrow_replicated<T, EPW>(M, P, mu_g, N, e, lc, R0, R, X, near, shw_tab, sct, pool);
   } else {
   // ---- narrowphase (round 5).  Each near pair's contacts are formed by the lane whose broadphase found it, from
   // the segments it holds in registers -- the closed-form sphere / capsule rules of gs_pairs.h self_pair (the
@@ -753,11 +792,12 @@ __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M
   constexpr int kLC = team_lc<T>(), kSt = kTeamSt;
   constexpr int kNone = 0x7fffffff;
   const int wl = threadIdx.x & 63;
-  const int team = threadIdx.x >> 2;
-  float* lslot = shw_tab + wl;                        // [f + kSt * slot][64 lanes]
-  float* tstg = shw_tab + kLC * kSt * 64 + team;      // [f + kSt * rank][TPW teams]
-  static_assert(kLC * kSt * 64 + T::NPK * kSt * TPW <= shw_size<T>(), "contact staging fits the table");
-  __syncthreads();  // an earlier user of the table (the TERR query list, a previous substep) is done with it
+  const int team = wl >> 2;
+  float* lslot = shw_tab + wl;                        // [f + kSt * slot][WL lanes]
+  float* tstg = shw_tab + kLC * kSt * WL + team;      // [f + kSt * rank][TPW teams]
+  static_assert(kLC * kSt * WL + T::NPK * kSt * TPW <= shw_size<T>() / WaveForm<EPW>::WAVES,
+                "contact staging fits the wave's slice of the table");
+  team_sync<EPW>();  // an earlier user of the table (the TERR query list, a previous substep) is done with it
   const float coff = P.contact_offset;
   int cnt = 0;  // the lane's contacts (all of them: the team's count caps at NPK)
   int key[kLC];
@@ -858,15 +898,15 @@ __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M
         slot = kn < km ? m : -1;
       }
       if (slot >= 0) {
-        float* o = lslot + kSt * slot * 64;
+        float* o = lslot + kSt * slot * WL;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          o[k * 64] = 0.5f * ((pa[c][k] - ra * nn[k]) + (pb[c][k] + rb * nn[k]));
-          o[(3 + k) * 64] = nn[k];
+          o[k * WL] = 0.5f * ((pa[c][k] - ra * nn[k]) + (pb[c][k] + rb * nn[k]));
+          o[(3 + k) * WL] = nn[k];
         }
-        o[6 * 64] = sep;
-        o[7 * 64] = __int_as_float(sha);
-        o[8 * 64] = __int_as_float(shb);
+        o[6 * WL] = sep;
+        o[7 * WL] = __int_as_float(sha);
+        o[8 * WL] = __int_as_float(shb);
 #pragma unroll
         for (int i = 0; i < kLC; ++i) key[i] = i == slot ? kn : key[i];
       }
@@ -908,13 +948,13 @@ __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M
 #pragma unroll
     for (int i = 0; i < kLC; ++i) {
       if (i < cnt && rk[i] < T::NPK) {
-        const float* src = lslot + kSt * i * 64;
+        const float* src = lslot + kSt * i * WL;
         float* dst = tstg + kSt * rk[i] * TPW;
 #pragma unroll
-        for (int f = 0; f < kSt; ++f) dst[f * TPW] = src[f * 64];
+        for (int f = 0; f < kSt; ++f) dst[f * TPW] = src[f * WL];
       }
     }
-    __syncthreads();
+    team_sync<EPW>();
     cnt_team = cnt_team < T::NPK ? cnt_team : T::NPK;
 #pragma unroll
     for (int r = 0; r < T::NPK; ++r) {
@@ -980,7 +1020,7 @@ __device__ __forceinline__ float terrain_candidate(const DevParams& P, const flo
   return dist;
 }
 
-template <class T, bool TERR, bool TGS>
+template <class T, bool TERR, bool TGS, int EPW>
 __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, const float* __restrict__ mdl,
                                              const DevParams& P, TeamState<T>& s, const float* tau,
                                              const float* __restrict__ mu_t, int N, int e, int lc,
@@ -1101,7 +1141,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
     // pose table (rewritten before each use there), kQItem floats per query: centre, radius, found, sep, normal.
     constexpr int kQItem = 9;
     static_assert(T::NPK > 0 && kShW * T::NS >= kQItem * (CC * LN + RC), "query list fits the pose table");
-    float* ql = shw_tab;  // (the workgroup's table; a workgroup is one wave)
+    float* ql = shw_tab;  // (the wave's slice of the workgroup's table)
     const int wl = threadIdx.x & 63;
     const unsigned long long below = (1ull << wl) - 1ull;
     int slot[NQ];
@@ -1120,7 +1160,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       }
       cnt += __popcll(bal);
     }
-    __syncthreads();
+    team_sync<EPW>();
 #ifdef GS_PHASE_PROFILE
     const long long tq1 = clock64();
 #endif
@@ -1137,7 +1177,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       it[5] = st;
       it[6] = nt[0]; it[7] = nt[1]; it[8] = nt[2];
     }
-    __syncthreads();
+    team_sync<EPW>();
 #ifdef GS_PHASE_PROFILE
     if ((threadIdx.x & 63) == 0) {  // mesh query phases: [50] the may_contact culls, [51] the scans, [52] queries
       const long long tq2 = clock64();
@@ -1228,7 +1268,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   int npc = 0;
   float* pool = rows_own + RS::POOL * RW;
   if constexpr (T::NPK > 0) {
-    if (P.self_collide) npc = team_self_contacts<T>(M, cm, P, mu_t, kTeamsPerBlock, 0, lc, R0, R, X, shw_tab, sct, pool);
+    if (P.self_collide) npc = team_self_contacts<T, EPW>(M, cm, P, mu_t, kTeamsPerBlock, 0, lc, R0, R, X, shw_tab, sct, pool);
   }
   GS_PROF(11)  // self-collision prepass
 #pragma unroll
@@ -1761,8 +1801,8 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       o[RS::P_CB * RW] = (float)(cb == ca ? -1 : cb);
     }
   }
-  // the sweeps read other lanes' records: make this wave's LDS writes visible (one-wave block)
-  __syncthreads();
+  // the sweeps read other lanes' records: make this wave's LDS writes visible
+  team_sync<EPW>();
 
   GS_PROF(3)  // contact records
   // The factorisation and the free velocity are read again only after the sweeps (back-substitution): they wait
@@ -2030,7 +2070,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
 #pragma unroll
     for (int k = 0; k < CL; ++k) wcp[k] = wc[k];
   }
-  __syncthreads();  // the next substep rewrites the records other lanes just read
+  team_sync<EPW>();  // the next substep rewrites the records other lanes just read
   stash_io(false);
 
   GS_PROF(4)  // PGS
@@ -2198,8 +2238,27 @@ __device__ __forceinline__ int xcd_block(int b, int G) {
   return x * per + (x < rem ? x : rem) + q;
 }
 
-template <class T, bool TERR, bool TGS>
-__global__ __launch_bounds__(kTeamBlock, 1) void k_simulate_team(const DevModel* __restrict__ M, DevParams P,
+// A thread's place in the launch: its column of the workgroup's LDS tables, its chain (lane of the team) and its
+// env; a wave's lanes beyond its EPW teams are off (e = N: they stage, then leave with the lanes of envs past N)
+struct TeamLane {
+  int wave, col, lc, e;
+  bool on;
+};
+template <class T, int EPW>
+__device__ __forceinline__ TeamLane team_lane(int N) {
+  constexpr int LN = T::T_LANES;
+  static_assert(WaveForm<EPW>::WAVES == 1 || shw_size<T>() % WaveForm<EPW>::WAVES == 0, "every wave its own slice");
+  TeamLane t;
+  t.wave = WaveForm<EPW>::kWhole ? 0 : (int)(threadIdx.x / GS_WAVE);
+  t.col = team_column<EPW>();
+  t.lc = threadIdx.x & (LN - 1);
+  t.on = WaveForm<EPW>::kWhole || (int)(threadIdx.x & (GS_WAVE - 1)) < WaveForm<EPW>::LANES;
+  t.e = t.on ? (xcd_block(blockIdx.x, gridDim.x) * kTeamBlock + t.col) / LN : N;
+  return t;
+}
+
+template <class T, bool TERR, bool TGS, int EPW>
+__global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(const DevModel* __restrict__ M, DevParams P,
                                                                  SimBuffers B, const float* __restrict__ tau_aos) {
   constexpr int LN = T::T_LANES, CL = T::T_CL, ND = T::ND;
   __shared__ float mdl[CM<T>::NP * LN];
@@ -2212,32 +2271,36 @@ __global__ __launch_bounds__(kTeamBlock, 1) void k_simulate_team(const DevModel*
   __shared__ float stash_tab[team_stash_size<T>() * kTeamBlock];
   stage_chain_model<T>(M, mdl);
   stage_shape_consts<T>(M, sct);
-  const int lc = threadIdx.x & (LN - 1);
-  const int e = (xcd_block(blockIdx.x, gridDim.x) * kTeamBlock + threadIdx.x) / LN;
-  for (int sh = lc; sh < T::NS; sh += LN)
-    mu_tab[sh * kTeamsPerBlock + (threadIdx.x >> 2)] = e < B.N ? B.mu[(size_t)sh * B.N + e] : 1.f;
+  // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
+  // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
+  const TeamLane tl = team_lane<T, EPW>(B.N);
+  const int lc = tl.lc, e = tl.e, col = tl.col;
+  if (tl.on)
+    for (int sh = lc; sh < T::NS; sh += LN)
+      mu_tab[sh * kTeamsPerBlock + (col >> 2)] = e < B.N ? B.mu[(size_t)sh * B.N + e] : 1.f;
   __syncthreads();
   if (e >= B.N) return;
-  const float* mu_t = mu_tab + (threadIdx.x >> 2);
+  const float* mu_t = mu_tab + (col >> 2);
+  float* shw_wave = shw_tab + tl.wave * (shw_size<T>() / WaveForm<EPW>::WAVES);
   const int N = B.N;
   TeamState<T> s;
   team_load<T>(B.state, N, e, lc, s);
   float tau[CL];
 #pragma unroll
   for (int k = 0; k < CL; ++k) tau[k] = tau_aos ? tau_aos[(size_t)e * ND + lc * CL + k] : 0.f;
-  float* own = rows + threadIdx.x;
-  const float* team = rows + (threadIdx.x & ~(LN - 1));
+  float* own = rows + col;
+  const float* team = rows + (col & ~(LN - 1));
   GS_PROF_DECL
   for (int sstep = 0; sstep < P.substeps; ++sstep) {
     const bool last = (sstep == P.substeps - 1) && P.collect;
-    substep_team<T, TERR, TGS>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, nullptr, shw_tab, sct, stash_tab + threadIdx.x GS_PROF_ARGS);
+    substep_team<T, TERR, TGS, EPW>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, nullptr, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
   }
   team_store<T>(B.state, N, opaque_index(e), opaque_index(lc), s);
   GS_PROF_FLUSH
 }
 
-template <class T, bool TERR, bool TGS>
-__global__ __launch_bounds__(kTeamBlock, 1) void k_pd_step_team(const DevModel* __restrict__ M, DevParams P,
+template <class T, bool TERR, bool TGS, int EPW>
+__global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(const DevModel* __restrict__ M, DevParams P,
                                                                 SimBuffers B, PdDev A) {
   constexpr int LN = T::T_LANES, CL = T::T_CL, ND = T::ND, NB = T::NB;
   __shared__ float mdl[CM<T>::NP * LN];
@@ -2250,19 +2313,23 @@ __global__ __launch_bounds__(kTeamBlock, 1) void k_pd_step_team(const DevModel* 
   __shared__ float stash_tab[team_stash_size<T>() * kTeamBlock];
   stage_chain_model<T>(M, mdl);
   stage_shape_consts<T>(M, sct);
-  const int lc = threadIdx.x & (LN - 1);
-  const int e = (xcd_block(blockIdx.x, gridDim.x) * kTeamBlock + threadIdx.x) / LN;
-  for (int sh = lc; sh < T::NS; sh += LN)
-    mu_tab[sh * kTeamsPerBlock + (threadIdx.x >> 2)] = e < B.N ? B.mu[(size_t)sh * B.N + e] : 1.f;
+  // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
+  // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
+  const TeamLane tl = team_lane<T, EPW>(B.N);
+  const int lc = tl.lc, e = tl.e, col = tl.col;
+  if (tl.on)
+    for (int sh = lc; sh < T::NS; sh += LN)
+      mu_tab[sh * kTeamsPerBlock + (col >> 2)] = e < B.N ? B.mu[(size_t)sh * B.N + e] : 1.f;
   __syncthreads();
   if (e >= B.N) return;
-  const float* mu_t = mu_tab + (threadIdx.x >> 2);
+  const float* mu_t = mu_tab + (col >> 2);
+  float* shw_wave = shw_tab + tl.wave * (shw_size<T>() / WaveForm<EPW>::WAVES);
   const int N = B.N;
   TeamState<T> s;
   team_load<T>(B.state, N, e, lc, s);
   float tau[CL];
-  float* own = rows + threadIdx.x;
-  const float* team = rows + (threadIdx.x & ~(LN - 1));
+  float* own = rows + col;
+  const float* team = rows + (col & ~(LN - 1));
   const int sub = P.substeps;
   const int n_pd = A.decimation * sub;
   const int total = (A.decimation + A.extra) * sub;
@@ -2284,7 +2351,7 @@ __global__ __launch_bounds__(kTeamBlock, 1) void k_pd_step_team(const DevModel* 
     const bool last = ((it % sub) == sub - 1) && P.collect;
     GS_PROF(6)  // PD torque
     float* cf_aos = (it == total - 1) ? A.cf_out : nullptr;
-    substep_team<T, TERR, TGS>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, cf_aos, shw_tab, sct, stash_tab + threadIdx.x GS_PROF_ARGS);
+    substep_team<T, TERR, TGS, EPW>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, cf_aos, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
     if (it == n_pd - 1 && A.dof_out) {
       const size_t d0 = dof0();
 #pragma unroll
@@ -2311,8 +2378,9 @@ __global__ __launch_bounds__(kTeamBlock, 1) void k_pd_step_team(const DevModel* 
     o[7] = v[0]; o[8] = v[1]; o[9] = v[2];
     o[10] = s.w[0]; o[11] = s.w[1]; o[12] = s.w[2];
   }
-  if constexpr (!TERR) if (kTeamsPerBlock == 16 && A.tail_on) {  // (plane kernels only: the TERR form is at its
-                                                                    // register limit, the tail cost it 12 B scratch)
+  // (plane kernels only: the TERR form is at its register limit, the tail cost it 12 B scratch; the 16-envs-per-wave
+  // form only: a wave writes a whole 16-env slice of the reset masks -- launch_pd_team runs that form for a tail)
+  if constexpr (!TERR && EPW == 16) if (kTeamsPerBlock == 16 && A.tail_on) {
     // The AnymalTerrain tail (gymsim.h gs_pd_args.tail_*; gt_anymal_tail.h, the source of libgymtask's k_post_a)
     // on the outputs this wave has just stored (root, contacts, dofs, torques, the actions copy): lane 0 of each
     // team runs its env, so the separate post_a launch and its wait behind this kernel go away.  The wave's 16
@@ -2346,22 +2414,42 @@ __global__ __launch_bounds__(kTeamBlock, 1) void k_pd_step_team(const DevModel* 
 // the fused tail writes 16-env slices of the reset-mask words (one wave of 16 teams per workgroup)
 bool team_fused_tail_available() { return kTeamsPerBlock == 16; }
 
+// Envs per wave of a launch (WaveForm): DevParams::team_epw when the sim was created with GS_TEAM_ENVS_PER_WAVE set,
+// else the form measured fastest for the scene kind (profiles/r07_*).  A fused tail runs the 16 form
+// (its reset-mask slices are a wave's 16 envs); a GS_TEAM_BLOCK < 64 build has the one-wave form only.
+constexpr int kTeamEpwPlane = 4, kTeamEpwTerr = 16;
+static int team_epw(const DevParams& P, bool tail) {
+  if (kTeamBlock != GS_WAVE || tail) return 16;
+  const int w = P.team_epw > 0 ? P.team_epw : (P.has_terrain ? kTeamEpwTerr : kTeamEpwPlane);
+  return w == 8 || w == 4 ? w : 16;
+}
+// the launch of kernel form K<T, TERR, TGS, EPW> chosen by the scene (TERR, TGS) and the envs per wave
+#define GS_TEAM_LAUNCH_EPW(K, EPW, ...)                                                                      \
+  do {                                                                                                       \
+    const dim3 g_((unsigned)blocks), b_((unsigned)WaveForm<EPW>::THREADS);                                   \
+    if (P.has_terrain && P.tgs) hipLaunchKernelGGL((K<T, true, true, EPW>), g_, b_, 0, st, __VA_ARGS__);     \
+    else if (P.has_terrain) hipLaunchKernelGGL((K<T, true, false, EPW>), g_, b_, 0, st, __VA_ARGS__);        \
+    else if (P.tgs) hipLaunchKernelGGL((K<T, false, true, EPW>), g_, b_, 0, st, __VA_ARGS__);                \
+    else hipLaunchKernelGGL((K<T, false, false, EPW>), g_, b_, 0, st, __VA_ARGS__);                          \
+  } while (0)
+#define GS_TEAM_LAUNCH(K, epw, ...)                              \
+  do {                                                           \
+    if constexpr (kTeamBlock == GS_WAVE) {                       \
+      if ((epw) == 8) { GS_TEAM_LAUNCH_EPW(K, 8, __VA_ARGS__); break; }  \
+      if ((epw) == 4) { GS_TEAM_LAUNCH_EPW(K, 4, __VA_ARGS__); break; }  \
+    }                                                            \
+    GS_TEAM_LAUNCH_EPW(K, 16, __VA_ARGS__);                      \
+  } while (0)
+
 template <class T>
 hipError_t launch_sim_team(const DevModel* M, const DevParams& P, const SimBuffers& B, const float* tau,
                            hipStream_t st) {
   if constexpr (T::HAS_TEAM) {
     static_assert(T::NR == T::NB, "the lane team reports contact forces per body (no kept fixed-joint links)");
     const long lanes = (long)B.N * T::T_LANES;
-    const int blocks = (int)((lanes + kTeamBlock - 1) / kTeamBlock);
+    const int blocks = (int)((lanes + kTeamBlock - 1) / kTeamBlock);  // a workgroup holds kTeamBlock / 4 envs in every form
     // trimesh terrain: mesh queries by the candidates' owner lanes; TGS / PGS
-    if (P.has_terrain && P.tgs)
-      hipLaunchKernelGGL((k_simulate_team<T, true, true>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, tau);
-    else if (P.has_terrain)
-      hipLaunchKernelGGL((k_simulate_team<T, true, false>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, tau);
-    else if (P.tgs)
-      hipLaunchKernelGGL((k_simulate_team<T, false, true>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, tau);
-    else
-      hipLaunchKernelGGL((k_simulate_team<T, false, false>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, tau);
+    GS_TEAM_LAUNCH(k_simulate_team, team_epw(P, false), M, P, B, tau);
     return hipGetLastError();
   } else {
     return hipErrorInvalidConfiguration;
@@ -2372,14 +2460,7 @@ hipError_t launch_pd_team(const DevModel* M, const DevParams& P, const SimBuffer
   if constexpr (T::HAS_TEAM) {
     const long lanes = (long)B.N * T::T_LANES;
     const int blocks = (int)((lanes + kTeamBlock - 1) / kTeamBlock);
-    if (P.has_terrain && P.tgs)
-      hipLaunchKernelGGL((k_pd_step_team<T, true, true>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, A);
-    else if (P.has_terrain)
-      hipLaunchKernelGGL((k_pd_step_team<T, true, false>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, A);
-    else if (P.tgs)
-      hipLaunchKernelGGL((k_pd_step_team<T, false, true>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, A);
-    else
-      hipLaunchKernelGGL((k_pd_step_team<T, false, false>), dim3(blocks), dim3(kTeamBlock), 0, st, M, P, B, A);
+    GS_TEAM_LAUNCH(k_pd_step_team, team_epw(P, A.tail_on != 0), M, P, B, A);
     return hipGetLastError();
   } else {
     return hipErrorInvalidConfiguration;
