@@ -308,6 +308,12 @@ int gs_debug_terrain_query(gs_sim *sim, const float *centres, const float *radii
  * pipeline (synchronises `stream`), host buffers on the host backend. */
 int gs_debug_self_contacts(gs_sim *sim, int mode, float *out, int *count, void *stream);
 
+/* Test hook: the form of the lane-team kernels (kernel variant 2) that the sim's next gs_sim_simulate / gs_sim_pd_step
+ * launch without a fused tail runs: envs per wave (16, 8 or 4; GS_TEAM_ENVS_PER_WAVE at gs_sim_create, else the
+ * scene's default) and whether lanes 16..63 of its waves stay as row lanes (the 4-envs-per-wave plane form;
+ * GS_TEAM_ROW_LANES=0|1 at gs_sim_create, else the default).  -1 for a sim that runs another kernel. */
+int gs_debug_team_form(gs_sim *sim, int *envs_per_wave, int *row_lanes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,11 @@ gs_sim* gs_sim_create(int device, const gs_sim_params* p) {
     const int w = std::atoi(v);
     s->dp.team_epw = w == 16 || w == 8 || w == 4 ? w : 0;
   }
+  // A/B switch of the row lanes of the 4-envs-per-wave plane form (0 / 1), read once here; unset: the default
+  s->dp.team_row_lanes = -1;
+  if (const char* v = std::getenv("GS_TEAM_ROW_LANES")) {
+    if (v[0] == '0' || v[0] == '1') s->dp.team_row_lanes = v[0] - '0';
+  }
   return s;
 }
 
@@ -1068,6 +1073,14 @@ int gs_debug_self_contacts(gs_sim* s, int mode, float* out, int* count, void* st
   }
   const hipError_t e = s->topo->dbg_pool(s->d_model, s->dp, buffers(s), mode, out, count, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(e, "gs_debug_self_contacts (mode 1 needs a split-form topology)");
+}
+
+int gs_debug_team_form(gs_sim* s, int* envs_per_wave, int* row_lanes) {
+  if (ready(s, "gs_debug_team_form")) return -1;
+  if (!envs_per_wave || !row_lanes) return fail("gs_debug_team_form: bad arguments");
+  if (s->host || s->variant != 2) return fail("gs_debug_team_form: the sim does not run the lane-team kernels");
+  team_launch_form(s->dp, envs_per_wave, row_lanes);
+  return 0;
 }
 
 int gs_sim_kernel_variant(gs_sim* s) { return s ? s->variant : -1; }

@@ -96,6 +96,9 @@ struct DevParams {
   // lane-team kernels: envs per wave of a launch, 16 / 8 / 4 (GS_TEAM_ENVS_PER_WAVE at gs_sim_create); 0 = the
   // kernel's own default for the scene (gs_team.hip team_epw)
   int team_epw;
+  // row lanes of the 4-envs-per-wave plane form, 0 / 1 (GS_TEAM_ROW_LANES at gs_sim_create); -1 = the kernel's own
+  // default (gs_team.hip team_row_lanes)
+  int team_row_lanes;
 };
 #define GS_DOFP_FIELDS 6
 
@@ -135,6 +138,8 @@ struct PdDev {
 };
 
 bool team_fused_tail_available();  // gs_team.hip: the lane-team kernel can run PdDev's tail
+// gs_team.hip: the form of the sim's next lane-team launch without a fused tail (gs_debug_team_form)
+void team_launch_form(const DevParams& P, int* epw, int* row_lanes);
 
 typedef hipError_t (*launch_sim_fn)(const DevModel*, const DevParams&, const SimBuffers&, const float* tau,
                                     hipStream_t);

@@ -14,8 +14,8 @@
 //     the row itself read from lane c's LDS column (16 teams read 16 addresses, 4-way broadcast).
 // Rows are processed in the oracle's global order (root candidates, then chain 0, 1, ...), so
 // the iterates are the same projected Gauss-Seidel sequence, only the rounding order of the base
-// sums differs.  4096 envs -> 256 workgroups of 16 envs, each 1, 2 or 4 waves (WaveForm); per-chain model constants
-// are staged in LDS.
+// sums differs.  4096 envs -> 256 workgroups of 16 envs, each 1, 2 or 4 waves (WaveForm; the 4-wave plane form keeps
+// a wave's spare lanes as row lanes, ROWL); per-chain model constants are staged in LDS.
 #include <type_traits>
 
 #include "gs_internal.h"
@@ -165,11 +165,36 @@ struct WaveForm {
   static constexpr int WAVES = kTeamBlock / LANES;             // waves of a workgroup
   static constexpr int THREADS = kWhole ? kTeamBlock : GS_WAVE * WAVES;
 };
+// Row lanes (ROWL, the 4-envs-per-wave plane form only): lanes 16 .. 63 of a wave stay as three more
+// copies of the teams in lanes 0 .. 15.  Copy r = lane >> 4 of a team has the team's env, chain and LDS column and
+// runs the same instructions on the same inputs as copy 0 -- on CDNA a wave64 VALU instruction takes its four cycles
+// however many lanes are on, so the copies cost no issue slots -- except where the three rows (normal, two tangents)
+// of a chain candidate's record or of a self-contact pool entry are built: there copy r builds row r alone (copy 3
+// row 2 again: the same words to the same addresses) and the copies exchange the finished rows (from_copy) for the
+// Delassus couplings, so a record costs one row instead of three.  Whatever a copy writes to "its own column" of
+// LDS is the word copy 0 writes; global stores are copy 0's alone.  Bit-identical to the other forms
+// (tests/test_team_row_lanes_gpu.py); 4096 envs: 107.9 -> 98.8 us per launch (profiles/r08_*).
+// this thread's lane among the live lanes of its wave (with row lanes: of its copy)
+template <int EPW, bool ROWL>
+__device__ __forceinline__ int team_wave_lane() {
+  return threadIdx.x & (ROWL ? WaveForm<EPW>::LANES - 1 : GS_WAVE - 1);
+}
+// the contact row this lane builds with row lanes on
+__device__ __forceinline__ int team_row_of_copy() {
+  const int r = (threadIdx.x & (GS_WAVE - 1)) >> 4;
+  return r < 2 ? r : 2;
+}
+// x of copy q's lane of this thread's column (all four copies of a team take every branch together)
+__device__ __forceinline__ float from_copy(float x, int q) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 15) | (q << 4)) << 2),
+                                                                __builtin_bit_cast(int, x)));
+}
+__device__ __forceinline__ float sel3(int i, float a, float b, float c) { return i == 0 ? a : (i == 1 ? b : c); }
 // this thread's column of the workgroup's per-lane LDS tables (rows, the stash; column >> 2: its team's)
-template <int EPW>
+template <int EPW, bool ROWL = false>
 __device__ __forceinline__ int team_column() {
   if constexpr (WaveForm<EPW>::kWhole) return threadIdx.x;
-  else return (threadIdx.x / GS_WAVE) * WaveForm<EPW>::LANES + (threadIdx.x & (GS_WAVE - 1));
+  else return (threadIdx.x / GS_WAVE) * WaveForm<EPW>::LANES + team_wave_lane<EPW, ROWL>();
 }
 // Orders this wave's LDS (and global) writes before its other lanes' reads.  The one-wave workgroup keeps
 // __syncthreads() (its barrier folds away); a multi-wave workgroup must not couple its waves -- a wave whose envs
@@ -198,15 +223,16 @@ struct RowSlots {
   static constexpr int CL = T::T_CL;
   // A Z row's 9 components (base 6 | chain 3) plus c = J nu_f in PGS-owner order, four slots per lane:
   // lane l < 3 owns base 2l, base 2l+1 and chain component l (slot 4l+3 a zero pad), lane 3 holds
-  // only c (slot 15), so every lane's partial of u = c + Z w is the same three FMAs.  Rows 0 and 1 are
-  // stored interleaved (zs): a slot's row-0 and row-1 values are adjacent, one paired LDS load lands them
-  // in a register pair, and the two rows' partials are three v_pk_fma_f32 (round 6).
+  // only c (slot 15), so every lane's partial of u = c + Z w is the same three FMAs.  The three rows are
+  // stored interleaved (zs): a slot's row-0, row-1 and row-2 values are adjacent, so rows 0 and 1 still arrive by
+  // one paired LDS load, and a row is a base (zs(rr, 0)) with the same immediate slot offsets zs(0, s) whatever
+  // the row -- the row-lane form builds row rr with rr a per-lane value.
   static constexpr int ZROW = 16;
   static constexpr int RZROW = 16;
   static constexpr int CSLOT = 15;
   __device__ static constexpr int zslot(int comp) { return comp < 6 ? 4 * (comp >> 1) + (comp & 1) : 4 * (comp - 6) + 2; }
   // offset of row rr's slot s inside a record's Z block
-  __device__ static constexpr int zs(int rr, int s) { return rr < 2 ? 2 * s + rr : 2 * ZROW + s; }
+  __device__ static constexpr int zs(int rr, int s) { return 3 * s + rr; }
   // (C_SEP / R_SEP: the row's separation at the substep's start, for TGS's per-sub-step targets)
   static constexpr int C_DI = 3 * ZROW, C_G = C_DI + 3, C_TP = C_G + 3, C_TV = C_TP + 1,
                        C_MU = C_TV + 1, C_ACT = C_MU + 1, C_SEP = C_ACT + 1, PER_CONTACT = C_SEP + 1;
@@ -428,10 +454,11 @@ __device__ __forceinline__ void body_inertia(const float* R, const float* X, flo
 }
 
 // Jacobian rows of a contact point xc (relative to O) for the base dofs: row ax of [-[xc]x | I]
+// (ax may be a per-lane value -- the row-lane form -- so it selects among the three rows' entries; k is a constant)
 __device__ __forceinline__ float base_jac(const float* xc, int ax, int k) {
   if (k < 3) {
     const float m3[3][3] = {{0.f, xc[2], -xc[1]}, {-xc[2], 0.f, xc[0]}, {xc[1], -xc[0], 0.f}};
-    return m3[ax][k];
+    return sel3(ax, m3[0][k], m3[1][k], m3[2][k]);
   }
   return (ax == k - 3) ? 1.f : 0.f;
 }
@@ -600,7 +627,7 @@ __device__ __forceinline__ unsigned long long quad_or64(unsigned long long m) {
 // The replicated narrowphase (the round-4 path, now the fallback of team_self_contacts when a lane holds more
 // contacts than it stages): every lane publishes its chain's shapes' full poses (lane 0 also the root's) to the
 // team's LDS table, and each lane of a team runs gs_pairs.h self_contacts over the team's near pairs.
-template <class T, int EPW>
+template <class T, int EPW, bool ROWL>
 __device__ __forceinline__ int team_narrow_replicated(const DevModel* __restrict__ M, const DevParams& P,
                                                    const float* __restrict__ mu_g, int N, int e, int lc,
                                                    const float (&R0)[9], const float (&R)[T::T_CL][9],
@@ -608,7 +635,7 @@ __device__ __forceinline__ int team_narrow_replicated(const DevModel* __restrict
                                                    float* __restrict__ shw_tab, const float* __restrict__ sct,
                                                    float* __restrict__ pool) {
   constexpr int TPW = WaveForm<EPW>::TEAMS;  // (shw_tab: the wave's slice of the table)
-  const int team = (threadIdx.x & (GS_WAVE - 1)) >> 2;
+  const int team = team_wave_lane<EPW, ROWL>() >> 2;
   float* tab = shw_tab + team;
   team_sync<EPW>();  // the staging above may still be read
   // full shape poses for the narrowphase: R (9), centre (3), bounding-sphere centre (3)
@@ -663,7 +690,7 @@ __device__ __forceinline__ int team_narrow_replicated(const DevModel* __restrict
 // LDS table and runs the narrowphase, replicated in each lane of the teams concerned (gs_pairs.h self_contacts:
 // the pair order and rules of the one-env-per-lane solver and the oracle).  Returns the team's self-contact count
 // (the pool in the lane's own column).
-template <class T, int EPW>
+template <class T, int EPW, bool ROWL>
 __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M, const float* __restrict__ cm,
                                                   const DevParams& P, const float* __restrict__ mu_g, int N, int e,
                                                   int lc, const float (&R0)[9], const float (&R)[T::T_CL][9],
@@ -778,7 +805,7 @@ __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M
 #endif
   if constexpr (!team_closed_form<T>()) {
     // GJK pairs: the replicated narrowphase (every pair kind of gs_pairs.h self_pair)
-    return team_narrow_replicated<T, EPW>(M, P, mu_g, N, e, lc, R0, R, X, near, shw_tab, sct, pool);
+    return team_narrow_replicated<T, EPW, ROWL>(M, P, mu_g, N, e, lc, R0, R, X, near, shw_tab, sct, pool);
   } else {
   // ---- narrowphase (round 5).  Each near pair's contacts are formed by the lane whose broadphase found it, from
   // the segments it holds in registers -- the closed-form sphere / capsule rules of gs_pairs.h self_pair (the
@@ -791,7 +818,7 @@ __device__ __forceinline__ int team_self_contacts(const DevModel* __restrict__ M
   // (exact for the team's first NPK, team_lc), so no lane ever falls back to the replicated narrowphase.
   constexpr int kLC = team_lc<T>(), kSt = kTeamSt;
   constexpr int kNone = 0x7fffffff;
-  const int wl = threadIdx.x & 63;
+  const int wl = team_wave_lane<EPW, ROWL>();  // (row lanes: the copies share their team's slots)
   const int team = wl >> 2;
   float* lslot = shw_tab + wl;                        // [f + kSt * slot][WL lanes]
   float* tstg = shw_tab + kLC * kSt * WL + team;      // [f + kSt * rank][TPW teams]
@@ -1020,7 +1047,7 @@ __device__ __forceinline__ float terrain_candidate(const DevParams& P, const flo
   return dist;
 }
 
-template <class T, bool TERR, bool TGS, int EPW>
+template <class T, bool TERR, bool TGS, int EPW, bool ROWL>
 __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, const float* __restrict__ mdl,
                                              const DevParams& P, TeamState<T>& s, const float* tau,
                                              const float* __restrict__ mu_t, int N, int e, int lc,
@@ -1030,6 +1057,10 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
                                              const float* __restrict__ sct, float* __restrict__ stash GS_PROF_PARAM) {
   constexpr int CL = T::T_CL, CC = T::T_CC, RC = T::T_RC, NCH = T::T_NCH, LN = T::T_LANES;
   static_assert(NCH == LN && LN == 4, "lane teams are DPP quads with one chain per lane");
+  static_assert(!ROWL || (!TERR && EPW == 4), "row lanes: the 4-envs-per-wave plane form");
+  // a contact's rows built by this lane: all three one after another, or (row lanes) the one of its copy
+  constexpr int NROW = ROWL ? 1 : 3;
+  [[maybe_unused]] const int row_own = ROWL ? team_row_of_copy() : 0;
   using C = CM<T>;
   using RS = RowSlots<T>;
   uintptr_t mp = reinterpret_cast<uintptr_t>(Min);
@@ -1268,7 +1299,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   int npc = 0;
   float* pool = rows_own + RS::POOL * RW;
   if constexpr (T::NPK > 0) {
-    if (P.self_collide) npc = team_self_contacts<T, EPW>(M, cm, P, mu_t, kTeamsPerBlock, 0, lc, R0, R, X, shw_tab, sct, pool);
+    if (P.self_collide) npc = team_self_contacts<T, EPW, ROWL>(M, cm, P, mu_t, kTeamsPerBlock, 0, lc, R0, R, X, shw_tab, sct, pool);
   }
   GS_PROF(11)  // self-collision prepass
 #pragma unroll
@@ -1348,20 +1379,22 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
         if (act[j]) {
           const float xc[3] = {x[0], x[1], x[2] - r};
 #pragma unroll
-          for (int rr = 0; rr < 3; ++rr) {
+          for (int ri = 0; ri < NROW; ++ri) {
+            const int rr = ROWL ? row_own : ri;
             const int ax3 = (rr == 0) ? 2 : (rr == 1 ? 0 : 1);
-            float* row = rows_own + RS::chain(j) * RW;
+            float* row = rows_own + (RS::chain(j) + RS::zs(rr, 0)) * RW;
 #pragma unroll
-            for (int b = 0; b < 6; ++b) row[RS::zs(rr, RS::zslot(b)) * RW] = base_jac(xc, ax3, b);
+            for (int b = 0; b < 6; ++b) row[RS::zs(0, RS::zslot(b)) * RW] = base_jac(xc, ax3, b);
+            // component ax3 of S_lin + S_ang x xc (cross3's own expression), its operands selected by the row's axis
+            const float xa = sel3(ax3, xc[1], xc[2], xc[0]), xb = sel3(ax3, xc[2], xc[0], xc[1]);
 #pragma unroll
             for (int kk = 0; kk < CL; ++kk) {
               float v = 0.f;
               if (kk <= k) {
-                float tt[3];
-                cross3(S[kk], xc, tt);
-                v = S[kk][3 + ax3] + tt[ax3];
+                const float sa = sel3(ax3, S[kk][1], S[kk][2], S[kk][0]), sb = sel3(ax3, S[kk][2], S[kk][0], S[kk][1]);
+                v = sel3(ax3, S[kk][3], S[kk][4], S[kk][5]) + (sa * xb - sb * xa);
               }
-              row[RS::zs(rr, RS::zslot(6 + kk)) * RW] = v;
+              row[RS::zs(0, RS::zslot(6 + kk)) * RW] = v;
             }
           }
         }
@@ -1538,9 +1571,10 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       const int kb = T::T_ccb[j];
       float zr[3][6 + CL], dir[3];
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        float* row = rows_own + RS::chain(j) * RW;
-        auto Z = [&](int sl) -> float& { return row[RS::zs(rr, sl) * RW]; };
+      for (int ri = 0; ri < NROW; ++ri) {
+        const int rr = ROWL ? row_own : ri;
+        float* row = rows_own + (RS::chain(j) + RS::zs(rr, 0)) * RW;
+        auto Z = [&](int sl) -> float& { return row[RS::zs(0, sl) * RW]; };
         float zb[6], zc[CL];
         float cj = 0.f;
 #pragma unroll
@@ -1564,20 +1598,20 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
 #pragma unroll
           for (int b = 0; b < k; ++b) zb[b] -= Mbb[k][b] * zb[k];
         }
-        float d = 0.f;
+        float d = 0.f, zo[6 + CL];
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
           zb[b] *= sDb[b];
           d += zb[b] * zb[b];
           Z(RS::zslot(b)) = zb[b];
-          zr[rr][b] = zb[b];
+          zo[b] = zb[b];
         }
 #pragma unroll
         for (int k = 0; k < CL; ++k) {
           const float z = k <= kb ? zc[k] * sDc[k] : 0.f;
           d += z * z;
           Z(RS::zslot(6 + k)) = z;
-          zr[rr][6 + k] = z;
+          zo[6 + k] = z;
         }
         Z(3) = 0.f;  // pads: lanes 0-2 add no constant, lane 3 owns no component
         Z(7) = 0.f;
@@ -1586,8 +1620,17 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
         Z(13) = 0.f;
         Z(14) = 0.f;
         Z(RS::CSLOT) = cj;
-        dir[rr] = d > 0.f ? __builtin_amdgcn_rcpf(d) : 0.f;  // (d == 0: a row the chain cannot move along)
-        rec[(RS::C_DI + rr) * RW] = dir[rr];
+        const float di = d > 0.f ? __builtin_amdgcn_rcpf(d) : 0.f;  // (d == 0: a row the chain cannot move along)
+        rec[(RS::C_DI + rr) * RW] = di;
+        // the Delassus couplings below take all three rows: with row lanes each copy hands out the row it built
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          if (ROWL || q == ri) {
+#pragma unroll
+            for (int f = 0; f < 6 + CL; ++f) zr[q][f] = ROWL ? from_copy(zo[f], q) : zo[f];
+            dir[q] = ROWL ? from_copy(di, q) : di;
+          }
+        }
       }
       float g10 = 0.f, g20 = 0.f, g21 = 0.f;
 #pragma unroll
@@ -1634,6 +1677,10 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       float* rec = rows_own + RS::root(j) * RW;
       const float xc[3] = {TERR ? x[0] - r * rdir[0][0] : x[0], TERR ? x[1] - r * rdir[0][1] : x[1],
                            TERR ? x[2] - r * rdir[0][2] : x[2] - r};
+      // (all three rows in every copy, row lanes or not: with the row a constant the base Jacobian's zeros and ones
+      // fold into the elimination below, and the folded statements round differently from the same statements on
+      // a per-lane row -- measured, a few ulp in the state -- so a root record split over the copies would not be
+      // the word-for-word record of the other forms; root candidates are active only while a base lies on the ground)
       float zr[3][6], dir[3];
 #pragma unroll
       for (int rr = 0; rr < 3; ++rr) {
@@ -1652,15 +1699,15 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
 #pragma unroll
           for (int b = 0; b < k; ++b) zb[b] -= Mbb[k][b] * zb[k];
         }
+        float* row = rec + RS::zs(rr, 0) * RW;
+        auto Z = [&](int sl) -> float& { return row[RS::zs(0, sl) * RW]; };
         float d = 0.f;
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
           zb[b] *= sDb[b];
           d += zb[b] * zb[b];
-          rec[RS::zs(rr, RS::zslot(b)) * RW] = zb[b];
-          zr[rr][b] = zb[b];
+          Z(RS::zslot(b)) = zb[b];
         }
-        auto Z = [&](int sl) -> float& { return rec[RS::zs(rr, sl) * RW]; };
 #pragma unroll
         for (int k = 0; k < 3; ++k) {  // no chain components; pads as in the chain records
           Z(4 * k + 2) = 0.f;
@@ -1670,6 +1717,8 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
         Z(13) = 0.f;
         Z(14) = 0.f;
         Z(RS::CSLOT) = cj;
+#pragma unroll
+        for (int f = 0; f < 6; ++f) zr[rr][f] = zb[f];
         dir[rr] = d > 0.f ? __builtin_amdgcn_rcpf(d) : 0.f;  // (d == 0: a row the chain cannot move along)
         rec[(RS::R_DI + rr) * RW] = dir[rr];
       }
@@ -1703,10 +1752,12 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       const int cb = bb > 0 ? (bb - 1) / CL : -1, kb = bb > 0 ? (bb - 1) - cb * CL : -1;
       const float x[3] = {o[kPoolX * RW], o[(kPoolX + 1) * RW], o[(kPoolX + 2) * RW]};
       float zr[3][6], zc3[3][CL], dd[3];
+      static_assert(kPoolT1 == kPoolN + 3 && kPoolT2 == kPoolN + 6, "a pool entry's three directions are one stride apart");
 #pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        const int dofs = rr == 0 ? kPoolN : (rr == 1 ? kPoolT1 : kPoolT2);
-        const float d[3] = {o[dofs * RW], o[(dofs + 1) * RW], o[(dofs + 2) * RW]};
+      for (int ri = 0; ri < NROW; ++ri) {
+        const int rr = ROWL ? row_own : ri;
+        const float* dp = o + (kPoolN + 3 * rr) * RW;
+        const float d[3] = {dp[0], dp[RW], dp[2 * RW]};
         float zc[CL], zbc[6];
         float cpart = 0.f;
 #pragma unroll
@@ -1738,10 +1789,20 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
         }
         float own = 0.f, db = 0.f;
 #pragma unroll
-        for (int b = 0; b < 6; ++b) { zb[b] *= sDb[b]; db += zb[b] * zb[b]; zr[rr][b] = zb[b]; }
+        for (int b = 0; b < 6; ++b) { zb[b] *= sDb[b]; db += zb[b] * zb[b]; }
 #pragma unroll
-        for (int k = 0; k < CL; ++k) { zc[k] *= sDc[k]; own += zc[k] * zc[k]; zc3[rr][k] = zc[k]; }
-        dd[rr] = db + quad_sum(own);
+        for (int k = 0; k < CL; ++k) { zc[k] *= sDc[k]; own += zc[k] * zc[k]; }
+        const float ddo = db + quad_sum(own);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {  // (row lanes: each copy hands out the row it built)
+          if (ROWL || q == ri) {
+#pragma unroll
+            for (int b = 0; b < 6; ++b) zr[q][b] = ROWL ? from_copy(zb[b], q) : zb[b];
+#pragma unroll
+            for (int k = 0; k < CL; ++k) zc3[q][k] = ROWL ? from_copy(zc[k], q) : zc[k];
+            dd[q] = ROWL ? from_copy(ddo, q) : ddo;
+          }
+        }
         const float cj = quad_sum(cpart);
         // distributed components: chain A / B component lc (from lane ca / cb), base 2 lc, 2 lc + 1
         float za = 0.f, zbb = 0.f;
@@ -2239,25 +2300,27 @@ __device__ __forceinline__ int xcd_block(int b, int G) {
 }
 
 // A thread's place in the launch: its column of the workgroup's LDS tables, its chain (lane of the team) and its
-// env; a wave's lanes beyond its EPW teams are off (e = N: they stage, then leave with the lanes of envs past N)
+// env; a wave's lanes beyond its EPW teams are off (e = N: they stage, then leave with the lanes of envs past N) --
+// or, with row lanes, stay as copies 1 .. 3 of the wave's teams (out: the copy that writes the launch's outputs)
 struct TeamLane {
   int wave, col, lc, e;
-  bool on;
+  bool on, out;
 };
-template <class T, int EPW>
+template <class T, int EPW, bool ROWL>
 __device__ __forceinline__ TeamLane team_lane(int N) {
   constexpr int LN = T::T_LANES;
   static_assert(WaveForm<EPW>::WAVES == 1 || shw_size<T>() % WaveForm<EPW>::WAVES == 0, "every wave its own slice");
   TeamLane t;
   t.wave = WaveForm<EPW>::kWhole ? 0 : (int)(threadIdx.x / GS_WAVE);
-  t.col = team_column<EPW>();
+  t.col = team_column<EPW, ROWL>();
   t.lc = threadIdx.x & (LN - 1);
-  t.on = WaveForm<EPW>::kWhole || (int)(threadIdx.x & (GS_WAVE - 1)) < WaveForm<EPW>::LANES;
+  t.on = WaveForm<EPW>::kWhole || ROWL || (int)(threadIdx.x & (GS_WAVE - 1)) < WaveForm<EPW>::LANES;
+  t.out = !ROWL || (int)(threadIdx.x & (GS_WAVE - 1)) < WaveForm<EPW>::LANES;
   t.e = t.on ? (xcd_block(blockIdx.x, gridDim.x) * kTeamBlock + t.col) / LN : N;
   return t;
 }
 
-template <class T, bool TERR, bool TGS, int EPW>
+template <class T, bool TERR, bool TGS, int EPW, bool ROWL>
 __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(const DevModel* __restrict__ M, DevParams P,
                                                                  SimBuffers B, const float* __restrict__ tau_aos) {
   constexpr int LN = T::T_LANES, CL = T::T_CL, ND = T::ND;
@@ -2273,7 +2336,7 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(con
   stage_shape_consts<T>(M, sct);
   // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
   // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
-  const TeamLane tl = team_lane<T, EPW>(B.N);
+  const TeamLane tl = team_lane<T, EPW, ROWL>(B.N);
   const int lc = tl.lc, e = tl.e, col = tl.col;
   if (tl.on)
     for (int sh = lc; sh < T::NS; sh += LN)
@@ -2292,14 +2355,14 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(con
   const float* team = rows + (col & ~(LN - 1));
   GS_PROF_DECL
   for (int sstep = 0; sstep < P.substeps; ++sstep) {
-    const bool last = (sstep == P.substeps - 1) && P.collect;
-    substep_team<T, TERR, TGS, EPW>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, nullptr, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
+    const bool last = (sstep == P.substeps - 1) && P.collect && tl.out;
+    substep_team<T, TERR, TGS, EPW, ROWL>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, nullptr, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
   }
-  team_store<T>(B.state, N, opaque_index(e), opaque_index(lc), s);
+  if (tl.out) team_store<T>(B.state, N, opaque_index(e), opaque_index(lc), s);
   GS_PROF_FLUSH
 }
 
-template <class T, bool TERR, bool TGS, int EPW>
+template <class T, bool TERR, bool TGS, int EPW, bool ROWL>
 __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(const DevModel* __restrict__ M, DevParams P,
                                                                 SimBuffers B, PdDev A) {
   constexpr int LN = T::T_LANES, CL = T::T_CL, ND = T::ND, NB = T::NB;
@@ -2315,7 +2378,7 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
   stage_shape_consts<T>(M, sct);
   // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
   // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
-  const TeamLane tl = team_lane<T, EPW>(B.N);
+  const TeamLane tl = team_lane<T, EPW, ROWL>(B.N);
   const int lc = tl.lc, e = tl.e, col = tl.col;
   if (tl.on)
     for (int sh = lc; sh < T::NS; sh += LN)
@@ -2348,11 +2411,11 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
         tau[k] = clampf(A.kp * (A.scale * aj + A.default_pos[lc * CL + k] - qj) - A.kd * qdj, -A.tlim, A.tlim);
       }
     }
-    const bool last = ((it % sub) == sub - 1) && P.collect;
+    const bool last = ((it % sub) == sub - 1) && P.collect && tl.out;
     GS_PROF(6)  // PD torque
     float* cf_aos = (it == total - 1) ? A.cf_out : nullptr;
-    substep_team<T, TERR, TGS, EPW>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, cf_aos, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
-    if (it == n_pd - 1 && A.dof_out) {
+    substep_team<T, TERR, TGS, EPW, ROWL>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, cf_aos, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
+    if (it == n_pd - 1 && A.dof_out && tl.out) {
       const size_t d0 = dof0();
 #pragma unroll
       for (int k = 0; k < CL; ++k) {
@@ -2361,15 +2424,18 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
       }
     }
   }
-  team_store<T>(B.state, N, opaque_index(e), opaque_index(lc), s);
-  const size_t d0 = dof0();
+  // (row lanes: copies 1 .. 3 hold the same state and write none of it)
+  if (tl.out) {
+    team_store<T>(B.state, N, opaque_index(e), opaque_index(lc), s);
+    const size_t d0 = dof0();
 #pragma unroll
-  for (int k = 0; k < CL; ++k) A.torques_out[d0 + k] = tau[k];
-  if (A.actions_copy) {
+    for (int k = 0; k < CL; ++k) A.torques_out[d0 + k] = tau[k];
+    if (A.actions_copy) {
 #pragma unroll
-    for (int k = 0; k < CL; ++k) A.actions_copy[d0 + k] = A.actions[d0 + k];
+      for (int k = 0; k < CL; ++k) A.actions_copy[d0 + k] = A.actions[d0 + k];
+    }
   }
-  if (A.root_out && lc == 0) {
+  if (A.root_out && lc == 0 && tl.out) {
     float* o = A.root_out + (size_t)e * 13;
     o[0] = s.p[0]; o[1] = s.p[1]; o[2] = s.p[2];
     o[3] = s.quat[0]; o[4] = s.quat[1]; o[5] = s.quat[2]; o[6] = s.quat[3];
@@ -2423,19 +2489,38 @@ static int team_epw(const DevParams& P, bool tail) {
   const int w = P.team_epw > 0 ? P.team_epw : (P.has_terrain ? kTeamEpwTerr : kTeamEpwPlane);
   return w == 8 || w == 4 ? w : 16;
 }
+// Row lanes of a launch with `epw` envs per wave (the ROWL forms: plane scenes, 4 envs per wave): DevParams::
+// team_row_lanes when the sim was created with GS_TEAM_ROW_LANES set, else the default measured
+constexpr bool kTeamRowLanesPlane = true;
+static bool team_row_lanes(const DevParams& P, int epw) {
+  if (kTeamBlock != GS_WAVE || epw != 4 || P.has_terrain) return false;
+  return P.team_row_lanes >= 0 ? P.team_row_lanes != 0 : kTeamRowLanesPlane;
+}
+void team_launch_form(const DevParams& P, int* epw, int* row_lanes) {
+  *epw = team_epw(P, false);
+  *row_lanes = team_row_lanes(P, *epw) ? 1 : 0;
+}
 // the launch of kernel form K<T, TERR, TGS, EPW> chosen by the scene (TERR, TGS) and the envs per wave
 #define GS_TEAM_LAUNCH_EPW(K, EPW, ...)                                                                      \
   do {                                                                                                       \
     const dim3 g_((unsigned)blocks), b_((unsigned)WaveForm<EPW>::THREADS);                                   \
-    if (P.has_terrain && P.tgs) hipLaunchKernelGGL((K<T, true, true, EPW>), g_, b_, 0, st, __VA_ARGS__);     \
-    else if (P.has_terrain) hipLaunchKernelGGL((K<T, true, false, EPW>), g_, b_, 0, st, __VA_ARGS__);        \
-    else if (P.tgs) hipLaunchKernelGGL((K<T, false, true, EPW>), g_, b_, 0, st, __VA_ARGS__);                \
-    else hipLaunchKernelGGL((K<T, false, false, EPW>), g_, b_, 0, st, __VA_ARGS__);                          \
+    if (P.has_terrain && P.tgs) hipLaunchKernelGGL((K<T, true, true, EPW, false>), g_, b_, 0, st, __VA_ARGS__);  \
+    else if (P.has_terrain) hipLaunchKernelGGL((K<T, true, false, EPW, false>), g_, b_, 0, st, __VA_ARGS__); \
+    else if (P.tgs) hipLaunchKernelGGL((K<T, false, true, EPW, false>), g_, b_, 0, st, __VA_ARGS__);         \
+    else hipLaunchKernelGGL((K<T, false, false, EPW, false>), g_, b_, 0, st, __VA_ARGS__);                   \
+  } while (0)
+// the row-lane forms (plane, 4 envs per wave)
+#define GS_TEAM_LAUNCH_ROWL(K, ...)                                                                          \
+  do {                                                                                                       \
+    const dim3 g_((unsigned)blocks), b_((unsigned)WaveForm<4>::THREADS);                                     \
+    if (P.tgs) hipLaunchKernelGGL((K<T, false, true, 4, true>), g_, b_, 0, st, __VA_ARGS__);                 \
+    else hipLaunchKernelGGL((K<T, false, false, 4, true>), g_, b_, 0, st, __VA_ARGS__);                      \
   } while (0)
 #define GS_TEAM_LAUNCH(K, epw, ...)                              \
   do {                                                           \
     if constexpr (kTeamBlock == GS_WAVE) {                       \
       if ((epw) == 8) { GS_TEAM_LAUNCH_EPW(K, 8, __VA_ARGS__); break; }  \
+      if ((epw) == 4 && team_row_lanes(P, 4)) { GS_TEAM_LAUNCH_ROWL(K, __VA_ARGS__); break; }  \
       if ((epw) == 4) { GS_TEAM_LAUNCH_EPW(K, 4, __VA_ARGS__); break; }  \
     }                                                            \
     GS_TEAM_LAUNCH_EPW(K, 16, __VA_ARGS__);                      \

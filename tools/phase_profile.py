@@ -5,7 +5,9 @@
 Loads libgymsim_prof.so (-DGS_PHASE_PROFILE) instead of libgymsim.so, runs AnymalTerrain
 steps and prints, per kernel launch and wave, the s_memtime cycles of each solver phase and the
 number of contacts each wave executes in the PGS sweeps (wave-uniform control flow: a contact
-costs a wave its full latency if ANY of its 16 envs has it active).
+costs a wave its full latency if ANY of its envs has it active).  The sums are divided by the waves
+the launch's form really runs (gs_debug_team_form: 16, 8 or 4 envs per wave; GS_TEAM_ENVS_PER_WAVE and
+GS_TEAM_ROW_LANES choose the form as for any sim).
 """
 import argparse
 import ctypes as C
@@ -43,7 +45,11 @@ def main():
     for i in range(a.steps):
         env.step(pool[i % 64])
     assert L.gs_debug_phase_cycles(buf, 64, 1) == 0
-    waves = (N * 4 + 63) // 64
+    epw, rowl = C.c_int(0), C.c_int(0)
+    assert L.gs_debug_team_form(env.sim.handle, C.byref(epw), C.byref(rowl)) == 0, "not a lane-team sim"
+    epw, rowl = epw.value, rowl.value
+    waves = (N + epw - 1) // epw  # the waves that hold an env (the others leave before the substeps)
+    print(f"form: {epw} envs per wave, row lanes {'on' if rowl else 'off'}")
     substeps = 5
     per = [buf[i] / (a.steps * waves) for i in range(16)]
     total = sum(per[:8]) + per[11]
@@ -72,7 +78,7 @@ def main():
     if buf[12]:
         print(f"self-collision narrowphase cycles per entry: {buf[13] / buf[12]:.0f}, of which the near pairs' "
               f"contacts in their lanes {buf[14] / buf[12]:.0f} (the rest: ranking, staging, pool entries); lanes of "
-              f"teams with a near pair per entry {buf[15] / buf[12]:.1f} of 64; lane 0's team near pairs per entry "
+              f"teams with a near pair per entry {buf[15] / buf[12]:.1f} of {64 if rowl else 4 * epw}; lane 0's team near pairs per entry "
               f"{buf[10] / buf[12]:.2f}")
 
 
