@@ -6,8 +6,8 @@
 //   ratio = exp(old_neglogp - neglogp); a = max(-adv ratio, -adv clamp(ratio, 1 - e, 1 + e))   (actor_loss)
 //   c = max((v - R)^2, (old_v + clamp(v - old_v, -e, e) - R)^2)  [clip_value] else (R - v)^2     (critic_loss)
 //   entropy = sum_a (0.5 + 0.5 log(2 pi) + log sigma)
-//   b = sum_a clamp_max(mu + 1.1, 0)^2 + clamp_min(mu - 1.1, 0)^2   (bound_loss; mu +- 1.1 rounded to fp16
-//       as torch's fp16 add does under autocast)
+//   b = sum_a clamp_max(mu + 1.1, 0)^2 + clamp_min(mu - 1.1, 0)^2   (bound_loss; with fp16 mu the sum mu +- 1.1 is
+//       rounded to fp16, as torch's fp16 add does under autocast; with f32 mu it is the plain f32 sum)
 //   loss = mean(a) + 0.5 mean(c) critic_coef - mean(entropy) entropy_coef + mean(b) bounds_loss_coef
 // and, in the same pass, d loss / d mu, d loss / d v, d loss / d logstd with PyTorch's autograd rules
 // (maximum: ties split the gradient; clamp: passes it inside [lo, hi] inclusive).  The torch statement
@@ -17,6 +17,10 @@
 // k_ppo_rows: one lane per row; per-workgroup partial sums of the four terms and of d/d logstd folded
 // in a fixed LDS tree -> part[block][4 + A]; k_ppo_finish: one workgroup adds the partials in block
 // order (deterministic; torch's reductions use another order: the loss agrees to fp32 rounding).
+// The actor term adds values of both signs, so its mean is small against its terms and the f32 rounding of
+// neglogp (tens, inside the ratio's exponent) shows in it: the row's actor term and its sums are float64 (slot 0
+// and slot 2 of a block's partials hold the sum's high and low f32 halves; the entropy, the same for every row,
+// is computed once in k_ppo_finish).  The gradients keep f32.
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,12 +34,20 @@ namespace {
 
 constexpr int kRows = 128;  // 128 workgroups for a 16384-row minibatch
 constexpr int kMaxA = 32;
-constexpr int kNT = 4 + kMaxA;  // partial slots per block: a, c, entropy, b, dlogstd[A]
+constexpr int kNT = 4 + kMaxA;  // partial slots per block: a (high), c, a (low), b, dlogstd[A]
+constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
 template <class T>
 __device__ __forceinline__ float ld(const T* p, size_t i) {
     if constexpr (sizeof(T) == 2) return __half2float(reinterpret_cast<const __half*>(p)[i]);
     else return reinterpret_cast<const float*>(p)[i];
+}
+
+// mu +- 1.1 of the bound loss in mu's own type T: torch's fp16 add rounds the f32 sum to fp16, its f32 add does not
+template <class T>
+__device__ __forceinline__ float bound_sum(float m, float c) {
+    if constexpr (sizeof(T) == 2) return __half2float(__float2half(m + c));
+    else return m + c;
 }
 
 // d max(p, q) / d (p, q) as PyTorch's maximum backward: the larger side, ties half each
@@ -44,35 +56,51 @@ __device__ __forceinline__ void max_grad(float p, float q, float& wp, float& wq)
     wq = 1.f - wp;
 }
 
+// the row's actor term max(-adv ratio, -adv clamp(ratio, 1 - e, 1 + e)) in float64: sq = sum_a ((x - mu) / sigma)^2
+__device__ __forceinline__ double actor_term(double sq, double sls, int A, float old_nlp, float adv, double e) {
+    const double r = exp((double)old_nlp - (0.5 * sq + kHalfLog2Pi * (double)A + sls));
+    const double rc = fmin(fmax(r, 1.0 - e), 1.0 + e);
+    return fmax(-((double)adv * r), -((double)adv * rc));
+}
+
 template <class TM, class TV>
 __global__ __launch_bounds__(kRows) void k_ppo_rows(const TM* __restrict__ mu, const TV* __restrict__ values,
                                                     const float* __restrict__ logstd, const float* __restrict__ act,
                                                     const float* __restrict__ old_nlp, const float* __restrict__ adv,
                                                     const float* __restrict__ old_v, const float* __restrict__ ret,
-                                                    int B, int A, float e, int clip_value, float cc, float ec,
-                                                    float bc, float* __restrict__ dmu, float* __restrict__ dv,
-                                                    float* __restrict__ part) {
+                                                    int B, int A, float e, double e_d, int clip_value, float cc,
+                                                    float ec, float bc, float* __restrict__ dmu,
+                                                    float* __restrict__ dv, float* __restrict__ part) {
     __shared__ float red[kNT][kRows];
+    __shared__ double red_a[kRows];
+    __shared__ double inv_sg[kMaxA];
     const int t = threadIdx.x;
+    if (t < A) inv_sg[t] = exp(-(double)logstd[t]);
+    __syncthreads();
     const int i = blockIdx.x * kRows + t;
     const float invB = 1.f / (float)B;
     const float half_log2pi = 0.5f * logf(2.f * 3.14159265358979323846f);
-    float ta = 0.f, tc = 0.f, te = 0.f, tb = 0.f;
+    float tc = 0.f, tb = 0.f;
+    double ta = 0.0;
     // this row's d/d logstd goes straight to its LDS column (no runtime-indexed register array)
     for (int a = 0; a < kMaxA; ++a) red[4 + a][t] = 0.f;
     if (i < B) {
-        // neglogp, entropy, bound loss
-        float sq = 0.f, sls = 0.f, ent = 0.f, bl = 0.f;
+        // neglogp, bound loss
+        float sq = 0.f, sls = 0.f, bl = 0.f;
+        double sq_d = 0.0, sls_d = 0.0;
         for (int a = 0; a < A; ++a) {
             const float m = ld(mu, (size_t)i * A + a);
             const float ls = logstd[a];
             const float sg = expf(ls);
-            const float z = (act[(size_t)i * A + a] - m) / sg;
+            const float x = act[(size_t)i * A + a];
+            const float z = (x - m) / sg;
+            const double z_d = ((double)x - (double)m) * inv_sg[a];
             sq += z * z;
             sls += ls;
-            ent += 0.5f + half_log2pi + logf(sg);
-            const float t1 = fminf(__half2float(__float2half(m + 1.1f)), 0.f);
-            const float t2 = fmaxf(__half2float(__float2half(m - 1.1f)), 0.f);
+            sq_d += z_d * z_d;
+            sls_d += (double)ls;
+            const float t1 = fminf(bound_sum<TM>(m, 1.1f), 0.f);
+            const float t2 = fmaxf(bound_sum<TM>(m, -1.1f), 0.f);
             bl += t1 * t1 + t2 * t2;
         }
         const float nlp = 0.5f * sq + half_log2pi * (float)A + sls;
@@ -80,7 +108,7 @@ __global__ __launch_bounds__(kRows) void k_ppo_rows(const TM* __restrict__ mu, c
         const float ad = adv[i];
         const float rc = fminf(fmaxf(r, 1.f - e), 1.f + e);
         const float p = -(ad * r), q = -(ad * rc);
-        const float av = fmaxf(p, q);
+        ta = actor_term(sq_d, sls_d, A, old_nlp[i], ad, e_d);
         // critic
         const float v = ld(values, i), ov = old_v[i], R = ret[i];
         float cv, dcdv;
@@ -97,7 +125,7 @@ __global__ __launch_bounds__(kRows) void k_ppo_rows(const TM* __restrict__ mu, c
             cv = (R - v) * (R - v);
             dcdv = 2.f * (v - R);
         }
-        ta = av; tc = cv; te = ent; tb = bl;
+        tc = cv; tb = bl;
         // gradients of the mean loss
         float wp, wq;
         max_grad(p, q, wp, wq);
@@ -108,45 +136,75 @@ __global__ __launch_bounds__(kRows) void k_ppo_rows(const TM* __restrict__ mu, c
             const float m = ld(mu, (size_t)i * A + a);
             const float sg = expf(logstd[a]);
             const float z = (act[(size_t)i * A + a] - m) / sg;
-            const float h1 = __half2float(__float2half(m + 1.1f)), h2 = __half2float(__float2half(m - 1.1f));
+            const float h1 = bound_sum<TM>(m, 1.1f), h2 = bound_sum<TM>(m, -1.1f);
             const float db = (h1 <= 0.f ? 2.f * fminf(h1, 0.f) : 0.f) + (h2 >= 0.f ? 2.f * fmaxf(h2, 0.f) : 0.f);
             dmu[(size_t)i * A + a] = dnlp * (-z / sg) + bc * invB * db;
             red[4 + a][t] = dnlp * (1.f - z * z) - ec * invB;
         }
         dv[i] = 0.5f * cc * invB * dcdv;
     }
-    red[0][t] = ta;
+    red_a[t] = ta;
+    red[0][t] = 0.f;
     red[1][t] = tc;
-    red[2][t] = te;
+    red[2][t] = 0.f;
     red[3][t] = tb;
     __syncthreads();
     for (int s = kRows / 2; s > 0; s >>= 1) {
-        if (t < s)
-            for (int k = 0; k < 4 + A; ++k) red[k][t] += red[k][t + s];
+        if (t < s) {
+            red_a[t] += red_a[t + s];
+            for (int k = 1; k < 4 + A; ++k) red[k][t] += red[k][t + s];
+        }
         __syncthreads();
     }
+    if (t == 0) {  // the actor sum as two f32 halves
+        const float hi = (float)red_a[0];
+        red[0][0] = hi;
+        red[2][0] = (float)(red_a[0] - (double)hi);
+    }
+    __syncthreads();
     if (t < 4 + A) part[(size_t)blockIdx.x * kNT + t] = red[t][0];
 }
 
 __device__ __forceinline__ float sum_partials(const float* __restrict__ part, int blocks, size_t stride, int i,
                                               bool on, float (*sh)[64]);
 
-__global__ __launch_bounds__(256) void k_ppo_finish(const float* __restrict__ part, int blocks, int A, float invB,
-                                                    float cc, float ec, float bc, float* __restrict__ loss,
-                                                    float* __restrict__ stats, float* __restrict__ dls) {
+__global__ __launch_bounds__(256) void k_ppo_finish(const float* __restrict__ part, int blocks, int A, int B,
+                                                    const float* __restrict__ logstd, float cc, float ec, float bc,
+                                                    float* __restrict__ loss, float* __restrict__ stats,
+                                                    float* __restrict__ dls) {
     // 4 lanes per slot add the blocks' partials (a fixed order, so the sums stay run-to-run identical)
     __shared__ float sh[4][64];
     __shared__ float m[4];
+    __shared__ double m_a;
     const int t = threadIdx.x;
+    const float invB = 1.f / (float)B;
     const float s = sum_partials(part, blocks, (size_t)kNT, t & 63, (t & 63) < 4 + A, sh);
-    if (t < 4) {
+    if (t == 1 || t == 3) {
         m[t] = s * invB;
         stats[t] = m[t];
-    } else if (t < 4 + A) {
+    } else if (t >= 4 && t < 4 + A) {
         dls[t - 4] = s;
     }
+    if (t < 64) {
+        // the actor mean in float64: lane l adds the two halves of the blocks b = l (mod 64), then a butterfly
+        double acc = 0.0;
+        for (int b = t; b < blocks; b += 64) acc += (double)part[(size_t)b * kNT] + (double)part[(size_t)b * kNT + 2];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (t == 0) {
+            m_a = acc / (double)B;
+            stats[0] = (float)m_a;
+        }
+    } else if (t == 64) {
+        // the entropy of the fixed sigma, the same for every row
+        const float half_log2pi = 0.5f * logf(2.f * 3.14159265358979323846f);
+        float ent = 0.f;
+        for (int a = 0; a < A; ++a) ent += 0.5f + half_log2pi + logf(expf(logstd[a]));
+        m[2] = ent;
+        stats[2] = ent;
+    }
     __syncthreads();
-    if (t == 0) *loss = m[0] + 0.5f * m[1] * cc - m[2] * ec + m[3] * bc;
+    if (t == 0) *loss = (float)(m_a + 0.5 * (double)m[1] * (double)cc - (double)m[2] * (double)ec + (double)m[3] * (double)bc);
 }
 
 template <class T>
@@ -205,12 +263,14 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
                                                    const float* __restrict__ logstd, const float* __restrict__ act,
                                                    const float* __restrict__ old_nlp, const float* __restrict__ adv,
                                                    const float* __restrict__ old_v, const float* __restrict__ ret,
-                                                   int B, int A, float e, int clip_value, float cc, float ec, float bc,
-                                                   __half* __restrict__ mu_out, float* __restrict__ dmu,
+                                                   int B, int A, float e, double e_d, int clip_value, float cc, float ec,
+                                                   float bc, __half* __restrict__ mu_out, float* __restrict__ dmu,
                                                    float* __restrict__ dv, float* __restrict__ part) {
     constexpr int H = 32 * NC, K4 = 8 * NC;
     __shared__ uint4 ws[(AM + 1) * H / 8];  // W_mu rows then w_v, fp16
     __shared__ float red[4][kNT];
+    __shared__ double red_a[4];
+    __shared__ double inv_sg[kMaxA];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, q = lane & 3;
     const int row = blockIdx.x * kHR + wave * 16 + (lane >> 2);
     const bool valid = row < B;
@@ -246,6 +306,7 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
 #pragma unroll
     for (int u = 0; u < WI; ++u)
         if (t + 256 * u < WN) wsh[t + 256 * u] = wtmp[u];
+    if (t < A) inv_sg[t] = exp(-(double)logstd[t]);
     __syncthreads();
     float m[AM];
     float vacc = 0.f;
@@ -272,12 +333,14 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
     const float invB = 1.f / (float)B;
     const float half_log2pi = 0.5f * logf(2.f * 3.14159265358979323846f);
     float dls[AM];
-    float ta = 0.f, tc = 0.f, te = 0.f, tb = 0.f;
+    float tc = 0.f, tb = 0.f;
+    double ta = 0.0;
 #pragma unroll
     for (int a = 0; a < AM; ++a) dls[a] = 0.f;
     if (valid) {
         const size_t i = (size_t)row;
-        float sq = 0.f, sls = 0.f, ent = 0.f, bl = 0.f;
+        float sq = 0.f, sls = 0.f, bl = 0.f;
+        double sq_d = 0.0, sls_d = 0.0;
 #pragma unroll
         for (int a = 0; a < AM; ++a) {
             if (a < A) {
@@ -286,9 +349,11 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
                 const float ls = lsv[a];
                 const float sg = expf(ls);
                 const float z = (xact[a] - m[a]) / sg;
+                const double z_d = ((double)xact[a] - (double)m[a]) * inv_sg[a];
                 sq += z * z;
                 sls += ls;
-                ent += 0.5f + half_log2pi + logf(sg);
+                sq_d += z_d * z_d;
+                sls_d += (double)ls;
                 const float t1 = fminf(rnd_h(m[a] + 1.1f), 0.f);
                 const float t2 = fmaxf(rnd_h(m[a] - 1.1f), 0.f);
                 bl += t1 * t1 + t2 * t2;
@@ -299,7 +364,7 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
         const float ad = r_adv;
         const float rc = fminf(fmaxf(r, 1.f - e), 1.f + e);
         const float p = -(ad * r), qq = -(ad * rc);
-        const float av = fmaxf(p, qq);
+        const double av = actor_term(sq_d, sls_d, A, r_old_nlp, ad, e_d);
         const float v = rnd_h(vacc + bv_f), ov = r_old_v, R = r_ret;
         float cv, dcdv;
         if (clip_value) {
@@ -333,7 +398,7 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
         }
         if (q == 0) {
             dv[i] = 0.5f * cc * invB * dcdv;
-            ta = av; tc = cv; te = ent; tb = bl;
+            ta = av; tc = cv; tb = bl;
         } else {
 #pragma unroll
             for (int a = 0; a < AM; ++a) dls[a] = 0.f;  // one contribution per row
@@ -341,7 +406,10 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
     }
     // the wave's 16 rows (butterfly, a fixed order), then the 4 waves in order -> part[block][kNT]
     float vals[4 + AM];
-    vals[0] = ta; vals[1] = tc; vals[2] = te; vals[3] = tb;
+    vals[0] = 0.f; vals[1] = tc; vals[2] = 0.f; vals[3] = tb;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ta += __shfl_xor(ta, o, 64);
+    if (lane == 0) red_a[wave] = ta;
 #pragma unroll
     for (int a = 0; a < AM; ++a) vals[4 + a] = dls[a];
 #pragma unroll
@@ -354,7 +422,15 @@ __global__ __launch_bounds__(256) void k_heads_fwd(const __half* __restrict__ hi
         }
     }
     __syncthreads();
-    if (t < 4 + A) part[(size_t)blockIdx.x * kNT + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if (t < 4 + A) {
+        float out = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+        if (t == 0 || t == 2) {  // the actor sum as two f32 halves
+            const double sa = (red_a[0] + red_a[1]) + (red_a[2] + red_a[3]);
+            const float hi = (float)sa;
+            out = t == 0 ? hi : (float)(sa - (double)hi);
+        }
+        part[(size_t)blockIdx.x * kNT + t] = out;
+    }
 }
 
 // one thread per column pair (actor columns 2p, 2p + 1 and the critic's) and row group: 512 / H groups of
@@ -519,14 +595,14 @@ extern "C" int rl_ppo_loss(const void* mu, int32_t mu_is_f16, const void* values
 #define RL_PPO_ROWS(TM, TV)                                                                                     \
     hipLaunchKernelGGL((k_ppo_rows<TM, TV>), dim3(blocks), dim3(kRows), 0, st, (const TM*)mu, (const TV*)values, \
                        logstd, actions, old_neglogp, advantages, old_values, returns, (int)rows, (int)num_actions, e, \
-                       (int)clip_value, cc, ec, bc, dmu, dvalues, partials)
+                       (double)e_clip, (int)clip_value, cc, ec, bc, dmu, dvalues, partials)
     if (mu_is_f16 && values_is_f16) RL_PPO_ROWS(__half, __half);
     else if (mu_is_f16) RL_PPO_ROWS(__half, float);
     else if (values_is_f16) RL_PPO_ROWS(float, __half);
     else RL_PPO_ROWS(float, float);
 #undef RL_PPO_ROWS
     if (int rc = launch_err("rl_ppo_loss")) return rc;
-    hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(256), 0, st, partials, blocks, (int)num_actions, 1.f / (float)rows,
+    hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(256), 0, st, partials, blocks, (int)num_actions, (int)rows, logstd,
                        cc, ec, bc, loss, stats, dlogstd);
     return launch_err("rl_ppo_loss finish");
 }
@@ -578,11 +654,11 @@ template <int AM>
 static void launch_heads_fwd(int blocks, size_t, hipStream_t st, const __half* hid, int ld, int acol, int ccol, int H,
                              const __half* wmu, const __half* bmu, const __half* wv, const __half* bv,
                              const float* logstd, const float* act, const float* old_nlp, const float* adv,
-                             const float* old_v, const float* ret, int B, int A, float e, int clip_value, float cc,
-                             float ec, float bc, __half* mu_out, float* dmu, float* dv, float* part) {
+                             const float* old_v, const float* ret, int B, int A, float e, double e_d, int clip_value,
+                             float cc, float ec, float bc, __half* mu_out, float* dmu, float* dv, float* part) {
 #define RL_HEADS_FWD(NC)                                                                                            \
     hipLaunchKernelGGL((k_heads_fwd<AM, NC>), dim3(blocks), dim3(256), 0, st, hid, ld, acol, ccol, wmu, bmu, wv, bv, \
-                       logstd, act, old_nlp, adv, old_v, ret, B, A, e, clip_value, cc, ec, bc, mu_out, dmu, dv, part)
+                       logstd, act, old_nlp, adv, old_v, ret, B, A, e, e_d, clip_value, cc, ec, bc, mu_out, dmu, dv, part)
     switch (H) {
         case 32: RL_HEADS_FWD(1); break;
         case 64: RL_HEADS_FWD(2); break;
@@ -622,10 +698,10 @@ extern "C" int rl_ppo_heads_loss(const void* hidden, int64_t ld, int32_t actor_c
     RL_HEADS_AM_SWITCH(num_actions, launch_heads_fwd, blocks, 0, st, (const __half*)hidden, (int)ld, (int)actor_col,
                        (int)critic_col, (int)hidden_size, (const __half*)w_mu, (const __half*)b_mu,
                        (const __half*)w_v, (const __half*)b_v, logstd, actions, old_neglogp, advantages, old_values,
-                       returns, (int)rows, (int)num_actions, e, (int)clip_value, cc, ec, bc, (__half*)mu_out, dmu,
+                       returns, (int)rows, (int)num_actions, e, (double)e_clip, (int)clip_value, cc, ec, bc, (__half*)mu_out, dmu,
                        dvalues, partials);
     if (int rc = launch_err("rl_ppo_heads_loss")) return rc;
-    hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(256), 0, st, partials, blocks, (int)num_actions, 1.f / (float)rows,
+    hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(256), 0, st, partials, blocks, (int)num_actions, (int)rows, logstd,
                        cc, ec, bc, loss, stats, dlogstd);
     return launch_err("rl_ppo_heads_loss finish");
 }

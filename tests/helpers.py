@@ -491,3 +491,84 @@ def perturbed(root, dof, idx, rng):
     d[:, :, 0] += rng.normal(0, 1e-6, d[:, :, 0].shape)
     d[:, :, 1] += rng.normal(0, 1e-5, d[:, :, 1].shape)
     return r, d
+
+
+# ---- PPO loss minibatches that reach every branch of the loss on known rows (test_ppo_loss_oracle.py,
+# ---- test_ppo_loss_gpu.py); every cycle below runs on (row + seed), the periods 8, 3, 5, 7 pairwise coprime
+PPO_E_CLIP = 0.2
+PPO_RATIO_TARGETS = (0.5, 0.79, 0.81, 0.95, 1.05, 1.19, 1.21, 2.0)  # >= 1 % from 1 -+ e_clip
+PPO_VDIFF = (-2.0, -0.5, 0.0, 0.5, 2.0)  # (values - old_values) / e_clip
+PPO_RETURN_OFFSETS = (-0.8, -0.07, 0.07, 0.8, -0.4, 0.4, 0.09)  # returns - (values + clipped value) / 2
+PPO_FAR_MU = (1.5, -1.5, 3.0, -3.0)  # every 10th element of mu: the bound loss active on both sides
+PPO_INPUTS = ("mu", "values", "logstd", "actions", "old_neglogp", "advantages", "old_values", "returns")
+PPO_ONE_ROW_SEEDS = range(120)  # a one-row minibatch is one cell: lcm(8, 3, 5) = 120 phases (>= 5 * 7, 40) reach all
+
+
+def ppo_minibatch(B, A, seed=0, mu_f16=False, values_f16=False, mu=None, values=None):
+    """{name: CPU tensor} of rl_ppo_loss's inputs (mu / values fp16 or f32, the rest f32) at e_clip = PPO_E_CLIP:
+    logstd in +-0.5; mu in +-1 with a tenth of its elements at PPO_FAR_MU; actions = mu + sigma N(0, 1);
+    old_neglogp = neglogp(mu, actions) + log(target), so that the ratio is PPO_RATIO_TARGETS[(row + seed) % 8];
+    advantages U(0.1, 2), -U(0.1, 2), exactly 0 by (row + seed) % 3; old_values = values - e_clip PPO_VDIFF[...];
+    returns = (values + clipped value) / 2 + PPO_RETURN_OFFSETS[...].  Everything is derived from the rounded mu /
+    values (given ones: the heads tests') in float64 and then rounded to f32."""
+    import torch
+    e = PPO_E_CLIP
+    rng = np.random.RandomState(1000 + seed)
+    idx = np.arange(B) + seed
+    logstd = rng.uniform(-0.5, 0.5, A).astype(np.float32)
+    m = rng.uniform(-1.0, 1.0, (B, A))
+    j = (np.arange(B * A) + seed).reshape(B, A)
+    m = np.where(j % 10 == 3, np.asarray(PPO_FAR_MU)[(j // 10) % 4], m)
+    v = rng.uniform(-1.0, 1.0, B)
+    if mu is None:
+        mu = torch.from_numpy(m).to(torch.float16 if mu_f16 else torch.float32)
+    if values is None:
+        values = torch.from_numpy(v).to(torch.float16 if values_f16 else torch.float32)
+    mu64, v64 = mu.double().numpy().reshape(B, A), values.double().numpy().reshape(B)
+    ls64 = logstd.astype(np.float64)
+    sigma = np.exp(ls64)
+    actions = (mu64 + sigma * rng.normal(size=(B, A))).astype(np.float32)
+    z = (actions.astype(np.float64) - mu64) / sigma
+    nlp = 0.5 * (z * z).sum(-1) + 0.5 * np.log(2.0 * np.pi) * A + ls64.sum()
+    old_neglogp = (nlp + np.log(np.asarray(PPO_RATIO_TARGETS)[idx % 8])).astype(np.float32)
+    mag = rng.uniform(0.1, 2.0, B)
+    advantages = np.where(idx % 3 == 0, mag, np.where(idx % 3 == 1, -mag, 0.0)).astype(np.float32)
+    old_values = (v64 - e * np.asarray(PPO_VDIFF)[idx % 5]).astype(np.float32)
+    ov64 = old_values.astype(np.float64)
+    vpc = ov64 + np.clip(v64 - ov64, -e, e)
+    returns = (0.5 * (v64 + vpc) + np.asarray(PPO_RETURN_OFFSETS)[idx % 7]).astype(np.float32)
+    t = torch.from_numpy
+    return dict(mu=mu.reshape(B, A).contiguous(), values=values.reshape(B).contiguous(), logstd=t(logstd),
+                actions=t(actions), old_neglogp=t(old_neglogp), advantages=t(advantages), old_values=t(old_values),
+                returns=t(returns))
+
+
+def ppo_heads_minibatch(B, H, A, seed=0):
+    """rl_ppo_heads_loss's inputs on a lattice where the heads are exact in any summation order: hidden_a, hidden_c
+    [B][H] in {-1, 0, 1}, w_mu [A][H], w_v [H] = k / 256 with |k| <= 2, b_mu, b_v = k / 256 with |k| <= 512 (every
+    4th b_mu at +-1.5 or +-2: mu beyond +-1.1), all fp16; so mu = hidden_a w_mu^T + b_mu and v = hidden_c w_v + b_v
+    are multiples of 1 / 256 below 8, exact in fp16.  Rows whose mu would come within 0.02 of +-1.1 are redrawn.
+    Then ppo_minibatch on that mu and v.  Returns (heads {name: CPU fp16 tensor}, minibatch)."""
+    import torch
+    rng = np.random.RandomState(2000 + seed)
+    ha = rng.randint(-1, 2, (B, H)).astype(np.float64)
+    hc = rng.randint(-1, 2, (B, H)).astype(np.float64)
+    w_mu = rng.randint(-2, 3, (A, H)) / 256.0
+    w_v = rng.randint(-2, 3, H) / 256.0
+    kb = rng.randint(-180, 181, A)
+    far = np.asarray([384, -384, 512, -512])[(np.arange(A) // 4) % 4]
+    b_mu = np.where(np.arange(A) % 4 == 2, far, kb) / 256.0
+    b_v = np.asarray([rng.randint(-128, 129) / 256.0])
+    for _ in range(100):
+        mu = ha @ w_mu.T + b_mu
+        bad = (np.abs(np.abs(mu) - 1.1) < 0.02).any(axis=1)
+        if not bad.any():
+            break
+        ha[bad] = rng.randint(-1, 2, (int(bad.sum()), H))
+    else:
+        raise AssertionError("ppo_heads_minibatch: could not move mu away from +-1.1")
+    v = hc @ w_v + b_v[0]
+    assert np.abs(mu).max() < 8 and np.abs(v).max() < 8
+    h = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.float16)  # noqa: E731
+    heads = dict(hidden_a=h(ha), hidden_c=h(hc), w_mu=h(w_mu), b_mu=h(b_mu), w_v=h(w_v), b_v=h(b_v))
+    return heads, ppo_minibatch(B, A, seed, mu=h(mu), values=h(v))
