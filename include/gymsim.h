@@ -314,6 +314,11 @@ int gs_debug_self_contacts(gs_sim *sim, int mode, float *out, int *count, void *
  * GS_TEAM_ROW_LANES=0|1 at gs_sim_create, else the default).  -1 for a sim that runs another kernel. */
 int gs_debug_team_form(gs_sim *sim, int *envs_per_wave, int *row_lanes);
 
+/* Test hook: whether that launch keeps the chains' contact records resident in the row lanes' registers across the
+ * Gauss-Seidel sweeps (the row-lane form only; GS_TEAM_RESIDENT_SWEEPS=0|1 at gs_sim_create, else the default; 0
+ * wherever row lanes are off).  -1 for a sim that runs another kernel. */
+int gs_debug_team_sweeps(gs_sim *sim, int *resident);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,11 @@ gs_sim* gs_sim_create(int device, const gs_sim_params* p) {
   if (const char* v = std::getenv("GS_TEAM_ROW_LANES")) {
     if (v[0] == '0' || v[0] == '1') s->dp.team_row_lanes = v[0] - '0';
   }
+  // A/B switch of the row-lane form's resident sweeps (0 / 1), read once here; unset: the default
+  s->dp.team_resident = -1;
+  if (const char* v = std::getenv("GS_TEAM_RESIDENT_SWEEPS")) {
+    if (v[0] == '0' || v[0] == '1') s->dp.team_resident = v[0] - '0';
+  }
   return s;
 }
 
@@ -1080,6 +1085,14 @@ int gs_debug_team_form(gs_sim* s, int* envs_per_wave, int* row_lanes) {
   if (!envs_per_wave || !row_lanes) return fail("gs_debug_team_form: bad arguments");
   if (s->host || s->variant != 2) return fail("gs_debug_team_form: the sim does not run the lane-team kernels");
   team_launch_form(s->dp, envs_per_wave, row_lanes);
+  return 0;
+}
+
+int gs_debug_team_sweeps(gs_sim* s, int* resident) {
+  if (ready(s, "gs_debug_team_sweeps")) return -1;
+  if (!resident) return fail("gs_debug_team_sweeps: bad arguments");
+  if (s->host || s->variant != 2) return fail("gs_debug_team_sweeps: the sim does not run the lane-team kernels");
+  *resident = team_launch_resident(s->dp);
   return 0;
 }
 

@@ -99,6 +99,9 @@ struct DevParams {
   // row lanes of the 4-envs-per-wave plane form, 0 / 1 (GS_TEAM_ROW_LANES at gs_sim_create); -1 = the kernel's own
   // default (gs_team.hip team_row_lanes)
   int team_row_lanes;
+  // resident sweeps of the row-lane form, 0 / 1 (GS_TEAM_RESIDENT_SWEEPS at gs_sim_create); -1 = the kernel's own
+  // default (gs_team.hip team_resident_sweeps)
+  int team_resident;
 };
 #define GS_DOFP_FIELDS 6
 
@@ -140,6 +143,7 @@ struct PdDev {
 bool team_fused_tail_available();  // gs_team.hip: the lane-team kernel can run PdDev's tail
 // gs_team.hip: the form of the sim's next lane-team launch without a fused tail (gs_debug_team_form)
 void team_launch_form(const DevParams& P, int* epw, int* row_lanes);
+int team_launch_resident(const DevParams& P);  // that launch's sweeps are the resident form (gs_debug_team_sweeps)
 
 typedef hipError_t (*launch_sim_fn)(const DevModel*, const DevParams&, const SimBuffers&, const float* tau,
                                     hipStream_t);

@@ -1047,7 +1047,7 @@ __device__ __forceinline__ float terrain_candidate(const DevParams& P, const flo
   return dist;
 }
 
-template <class T, bool TERR, bool TGS, int EPW, bool ROWL>
+template <class T, bool TERR, bool TGS, int EPW, bool ROWL, bool RES>
 __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, const float* __restrict__ mdl,
                                              const DevParams& P, TeamState<T>& s, const float* tau,
                                              const float* __restrict__ mu_t, int N, int e, int lc,
@@ -1900,14 +1900,41 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   // (bit-identical in the 4 lanes), the 3-row projection through the contact's Delassus couplings
   // runs replicated, and each lane updates only what it owns.
   static_assert(CL == 3, "component distribution assumes 3-dof chains");
-  float wA = 0.f, wA2 = 0.f, wC[NCH];
+  //
+  // Resident sweeps (RES, the row-lane form only): copy c = lane >> 4 of a team OWNS chain c.  It loads
+  // chain c's CC records into registers once per substep (the records do not change between the sweeps) and keeps the
+  // chain's velocity (wC[0], aC[0]) and impulses (lamc[0]); chain block c of a sweep runs in copy c alone and every
+  // copy then takes the base velocity from it (the hand-off), so the sweep is the same Gauss-Seidel sequence with
+  // each statement on the same values.  Root candidates and the pool run replicated in all copies as without RES.
+  static_assert(!RES || ROWL, "resident sweeps: the row-lane form");
+  constexpr int NOWN = RES ? 1 : NCH;  // chains whose velocity and impulses this lane keeps
+  [[maybe_unused]] const int cpy = RES ? (int)((threadIdx.x & (GS_WAVE - 1)) >> 4) : 0;
+  float wA = 0.f, wA2 = 0.f, wC[NOWN];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) wC[c] = 0.f;
-  float lamc[NCH][CC][3], lamr[RC > 0 ? RC : 1][3];
+  for (int c = 0; c < NOWN; ++c) wC[c] = 0.f;
+  float lamc[NOWN][CC][3], lamr[RC > 0 ? RC : 1][3];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c)
+  for (int c = 0; c < NOWN; ++c)
 #pragma unroll
     for (int j = 0; j < CC; ++j) lamc[c][j][0] = lamc[c][j][1] = lamc[c][j][2] = 0.f;
+  // (RES) the own chain's records: this lane's Z components and c | 1/G_rr, couplings | targets | mu | activity
+  struct OwnRec { float z[12], k[6], tp, tv, mu, act; };
+  struct NoRec {};
+  [[maybe_unused]] std::conditional_t<RES, OwnRec, NoRec> orec[CC];
+  if constexpr (RES) {
+#pragma unroll
+    for (int j = 0; j < CC; ++j) {
+      const float* rec = rows_team + cpy + RS::chain(j) * RW;
+      orec[j].act = rec[RS::C_ACT * RW];
+#pragma unroll
+      for (int i = 0; i < 12; ++i) orec[j].z[i] = rec[RS::zs(i >> 2, 4 * lc + (i & 3)) * RW];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) orec[j].k[i] = rec[(RS::C_DI + i) * RW];
+      orec[j].tp = rec[(TGS ? RS::C_SEP : RS::C_TP) * RW];  // (TGS: the separation, one word for both phases)
+      orec[j].tv = TGS ? orec[j].tp : rec[RS::C_TV * RW];
+      orec[j].mu = rec[RS::C_MU * RW];
+    }
+  }
 #pragma unroll
   for (int j = 0; j < RC; ++j) lamr[j][0] = lamr[j][1] = lamr[j][2] = 0.f;
   float wbp[6], wcp[CL];
@@ -1921,9 +1948,14 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   // (TGS is a template parameter: the PGS kernels carry none of its state, and its target is branch-free)
   constexpr bool tgs = TGS;
   const float hs = tgs ? h / (float)P.pos_iters : h, inv_hs = 1.f / hs;
-  [[maybe_unused]] float aA = 0.f, aA2 = 0.f, aC[NCH];
+  [[maybe_unused]] float aA = 0.f, aA2 = 0.f, aC[NOWN];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) aC[c] = 0.f;
+  for (int c = 0; c < NOWN; ++c) aC[c] = 0.f;
+  // (RES) the chains' velocities as every copy holds them without RES: chain c's from its owner copy
+  [[maybe_unused]] auto all_chains = [&](float x_own, float (&x)[NCH]) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) x[c] = from_copy(x_own, c);
+  };
   for (int it = 0; it < iters; ++it) {
     const int tsel = it < P.pos_iters ? RS::C_TP : RS::C_TV;
     const int rsel = it < P.pos_iters ? RS::R_TP : RS::R_TV;
@@ -1968,66 +2000,117 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
         wA2 = fmaf(z[9], dl2, fmaf(z[5], dl1, fmaf(z[1], dl0, wA2)));
       }
     }
-    // software-pipelined over the NCH*CC chain contacts: the next contact's whole record (activity,
-    // this lane's Z components and c, the Delassus block, target, mu) is loaded before this
-    // contact's (divergent) block, so its LDS latency overlaps the block
-    float nact, nz[12], nk[8];  // nk: 1/G_rr (3) | scaled couplings (3) | target (TGS: separation) | mu
-    auto fetch = [&](int n) {
-      const int cc = n / CC, j = n - (n / CC) * CC;
-      const float* rec = rows_team + cc + RS::chain(j) * RW;
-      nact = rec[RS::C_ACT * RW];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) nz[i] = rec[RS::zs(i >> 2, 4 * lc + (i & 3)) * RW];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) nk[i] = rec[(RS::C_DI + i) * RW];
-      nk[6] = rec[(tgs ? RS::C_SEP : tsel) * RW];
-      nk[7] = rec[RS::C_MU * RW];
-    };
-    fetch(0);
-#pragma unroll
-    for (int n = 0; n < NCH * CC; ++n) {
-      const int cc = n / CC, j = n - (n / CC) * CC;
-      float z[12], k8[8];
-      const float act_n = nact;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) z[i] = nz[i];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) k8[i] = nk[i];
-      // (the scheduler hoists all 12 records' loads to the top of the sweep and parks them in AGPRs;
-      // measured faster than keeping the prefetch one contact deep with a scheduling fence:
-      // 0.0886 vs 0.0915 ms per launch, profiles/r02o_experiments_team_pgs.txt)
-#ifdef GS_PGS_FENCE
-      __builtin_amdgcn_sched_barrier(0);  // (A/B: keep the prefetch one contact deep)
-#endif
-      if (n + 1 < NCH * CC) fetch(n + 1);
-      const bool a_o = act_n != 0.f;
+    if constexpr (RES) {
+      // chain block c in its owner copy, from the registers loaded above: the statements of the replicated form
+      // below on the same values.  One body of code for the four chains (c is a loop counter, the owner a lane mask).
 #ifdef GS_PHASE_PROFILE
-      if (__ballot(a_o) != 0ull) GS_PROF_COUNT(8, 1)  // chain contacts the wave executes
+#pragma unroll
+      for (int j = 0; j < CC; ++j) {  // chain contacts the wave executes (counted where lane 0 is on)
+        const unsigned long long m = __ballot(orec[j].act != 0.f);
+        for (int c = 0; c < NCH; ++c)
+          if ((m >> (16 * c)) & 0xffffull) GS_PROF_COUNT(8, 1)
+      }
 #endif
-      if (a_o) {
-        float u[4];
-        {  // the w terms last (they carry the Gauss-Seidel chain); rows 0 and 1 as register pairs
-          const f2 u01 = pk_fma(f2{z[0], z[4]}, f2{wA, wA},
-                                pk_fma(f2{z[1], z[5]}, f2{wA2, wA2}, pk_fma(f2{z[2], z[6]}, f2{wC[cc], wC[cc]},
-                                                                         f2{z[3], z[7]})));
-          u[0] = u01.x;
-          u[1] = u01.y;
+#pragma unroll 1
+      for (int c = 0; c < NCH; ++c) {
+        if (cpy == c) {
+#pragma unroll
+          for (int j = 0; j < CC; ++j) {
+            if (orec[j].act != 0.f) {
+              const float* z = orec[j].z;
+              const float* k8 = orec[j].k;
+              float u[4];
+              {
+                const f2 u01 = pk_fma(f2{z[0], z[4]}, f2{wA, wA},
+                                      pk_fma(f2{z[1], z[5]}, f2{wA2, wA2}, pk_fma(f2{z[2], z[6]}, f2{wC[0], wC[0]},
+                                                                               f2{z[3], z[7]})));
+                u[0] = u01.x;
+                u[1] = u01.y;
+              }
+              u[2] = fmaf(z[8], wA, fmaf(z[9], wA2, fmaf(z[10], wC[0], z[11])));
+              float tdi = pos ? orec[j].tp : orec[j].tv;
+              if constexpr (tgs) {
+                u[3] = fmaf(z[0], aA, fmaf(z[1], aA2, fmaf(z[2], aC[0], na * z[3])));
+                quad_sum4(u);
+                tdi = tgs_tdi(orec[j].tp, u[3], k8[0]);
+              } else {
+                quad_sum3(u);
+              }
+              float dl0, dl1, dl2;
+              contact_block(u[0], u[1], u[2], k8[0], k8[1], k8[2], k8[3], k8[4], k8[5], tdi, orec[j].mu, lamc[0][j],
+                            dl0, dl1, dl2);
+              wA = fmaf(z[8], dl2, fmaf(z[4], dl1, fmaf(z[0], dl0, wA)));
+              wA2 = fmaf(z[9], dl2, fmaf(z[5], dl1, fmaf(z[1], dl0, wA2)));
+              wC[0] = fmaf(z[10], dl2, fmaf(z[6], dl1, fmaf(z[2], dl0, wC[0])));
+            }
+          }
         }
-        u[2] = fmaf(z[8], wA, fmaf(z[9], wA2, fmaf(z[10], wC[cc], z[11])));
-        float tdi = k8[6];
-        if constexpr (tgs) {
-          u[3] = fmaf(z[0], aA, fmaf(z[1], aA2, fmaf(z[2], aC[cc], na * z[3])));
-          quad_sum4(u);
-          tdi = tgs_tdi(k8[6], u[3], k8[0]);
-        } else {
-          quad_sum3(u);
+        // the hand-off, with all four copies on: every copy takes the base velocity from chain c's owner
+        wA = from_copy(wA, c);
+        wA2 = from_copy(wA2, c);
+      }
+    } else {
+      // software-pipelined over the NCH*CC chain contacts: the next contact's whole record (activity,
+      // this lane's Z components and c, the Delassus block, target, mu) is loaded before this
+      // contact's (divergent) block, so its LDS latency overlaps the block
+      float nact, nz[12], nk[8];  // nk: 1/G_rr (3) | scaled couplings (3) | target (TGS: separation) | mu
+      auto fetch = [&](int n) {
+        const int cc = n / CC, j = n - (n / CC) * CC;
+        const float* rec = rows_team + cc + RS::chain(j) * RW;
+        nact = rec[RS::C_ACT * RW];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) nz[i] = rec[RS::zs(i >> 2, 4 * lc + (i & 3)) * RW];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) nk[i] = rec[(RS::C_DI + i) * RW];
+        nk[6] = rec[(tgs ? RS::C_SEP : tsel) * RW];
+        nk[7] = rec[RS::C_MU * RW];
+      };
+      fetch(0);
+#pragma unroll
+      for (int n = 0; n < NCH * CC; ++n) {
+        const int cc = n / CC, j = n - (n / CC) * CC;
+        float z[12], k8[8];
+        const float act_n = nact;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) z[i] = nz[i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k8[i] = nk[i];
+        // (the scheduler hoists all 12 records' loads to the top of the sweep and parks them in AGPRs;
+        // measured faster than keeping the prefetch one contact deep with a scheduling fence:
+        // 0.0886 vs 0.0915 ms per launch, profiles/r02o_experiments_team_pgs.txt)
+#ifdef GS_PGS_FENCE
+        __builtin_amdgcn_sched_barrier(0);  // (A/B: keep the prefetch one contact deep)
+#endif
+        if (n + 1 < NCH * CC) fetch(n + 1);
+        const bool a_o = act_n != 0.f;
+#ifdef GS_PHASE_PROFILE
+        if (__ballot(a_o) != 0ull) GS_PROF_COUNT(8, 1)  // chain contacts the wave executes
+#endif
+        if (a_o) {
+          float u[4];
+          {  // the w terms last (they carry the Gauss-Seidel chain); rows 0 and 1 as register pairs
+            const f2 u01 = pk_fma(f2{z[0], z[4]}, f2{wA, wA},
+                                  pk_fma(f2{z[1], z[5]}, f2{wA2, wA2}, pk_fma(f2{z[2], z[6]}, f2{wC[cc], wC[cc]},
+                                                                           f2{z[3], z[7]})));
+            u[0] = u01.x;
+            u[1] = u01.y;
+          }
+          u[2] = fmaf(z[8], wA, fmaf(z[9], wA2, fmaf(z[10], wC[cc], z[11])));
+          float tdi = k8[6];
+          if constexpr (tgs) {
+            u[3] = fmaf(z[0], aA, fmaf(z[1], aA2, fmaf(z[2], aC[cc], na * z[3])));
+            quad_sum4(u);
+            tdi = tgs_tdi(k8[6], u[3], k8[0]);
+          } else {
+            quad_sum3(u);
+          }
+          float dl0, dl1, dl2;
+          contact_block(u[0], u[1], u[2], k8[0], k8[1], k8[2], k8[3], k8[4], k8[5], tdi, k8[7], lamc[cc][j], dl0,
+                        dl1, dl2);
+          wA = fmaf(z[8], dl2, fmaf(z[4], dl1, fmaf(z[0], dl0, wA)));
+          wA2 = fmaf(z[9], dl2, fmaf(z[5], dl1, fmaf(z[1], dl0, wA2)));
+          wC[cc] = fmaf(z[10], dl2, fmaf(z[6], dl1, fmaf(z[2], dl0, wC[cc])));
         }
-        float dl0, dl1, dl2;
-        contact_block(u[0], u[1], u[2], k8[0], k8[1], k8[2], k8[3], k8[4], k8[5], tdi, k8[7], lamc[cc][j], dl0,
-                      dl1, dl2);
-        wA = fmaf(z[8], dl2, fmaf(z[4], dl1, fmaf(z[0], dl0, wA)));
-        wA2 = fmaf(z[9], dl2, fmaf(z[5], dl1, fmaf(z[1], dl0, wA2)));
-        wC[cc] = fmaf(z[10], dl2, fmaf(z[6], dl1, fmaf(z[2], dl0, wC[cc])));
       }
     }
     if constexpr (T::NPK > 0) {
@@ -2065,12 +2148,25 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
         if (p + 1 < T::NPK) pfetch(p + 1);
         if (p < npc) {
           float wa = 0.f, wb = 0.f, ana = 0.f, anb = 0.f;
+          if constexpr (RES) {
+            // chains A and B's velocities from their owner copies (ca / cb: the team's, the same in its four copies,
+            // which take this branch together; -1: the base body or B on A's chain, no chain term)
+            const float xa = from_copy(wC[0], ca & (NCH - 1)), xb = from_copy(wC[0], cb & (NCH - 1));
+            wa = ca >= 0 ? xa : 0.f;
+            wb = cb >= 0 ? xb : 0.f;
+            if constexpr (tgs) {
+              const float ya = from_copy(aC[0], ca & (NCH - 1)), yb = from_copy(aC[0], cb & (NCH - 1));
+              ana = ca >= 0 ? ya : 0.f;
+              anb = cb >= 0 ? yb : 0.f;
+            }
+          } else {
 #pragma unroll
-          for (int c = 0; c < NCH; ++c) {
-            wa = c == ca ? wC[c] : wa;
-            wb = c == cb ? wC[c] : wb;
-            ana = c == ca ? aC[c] : ana;
-            anb = c == cb ? aC[c] : anb;
+            for (int c = 0; c < NCH; ++c) {
+              wa = c == ca ? wC[c] : wa;
+              wb = c == cb ? wC[c] : wb;
+              ana = c == ca ? aC[c] : ana;
+              anb = c == cb ? aC[c] : anb;
+            }
           }
           float u[4];
 #pragma unroll
@@ -2096,8 +2192,12 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
           wA2 = fmaf(z[11], dl2, fmaf(z[6], dl1, fmaf(z[1], dl0, wA2)));
           const float da = fmaf(z[12], dl2, fmaf(z[7], dl1, z[2] * dl0));
           const float db = fmaf(z[13], dl2, fmaf(z[8], dl1, z[3] * dl0));
+          if constexpr (RES) {
+            wC[0] += (cpy == ca ? da : 0.f) + (cpy == cb ? db : 0.f);
+          } else {
 #pragma unroll
-          for (int c = 0; c < NCH; ++c) wC[c] += (c == ca ? da : 0.f) + (c == cb ? db : 0.f);
+            for (int c = 0; c < NCH; ++c) wC[c] += (c == ca ? da : 0.f) + (c == cb ? db : 0.f);
+          }
         }
       }
     }
@@ -2109,22 +2209,36 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       aA += wA;
       aA2 += wA2;
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) aC[c] += wC[c];
+      for (int c = 0; c < NOWN; ++c) aC[c] += wC[c];
     }
     if (it == P.pos_iters - 1) {
       if constexpr (tgs) {  // positions integrate the sub-steps' mean velocity (w space is linear)
         const float inv_n = 1.f / (float)P.pos_iters;
         float mC[NCH];
+        if constexpr (RES) {
+          all_chains(aC[0] * inv_n, mC);
+        } else {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) mC[c] = aC[c] * inv_n;
+          for (int c = 0; c < NCH; ++c) mC[c] = aC[c] * inv_n;
+        }
         gather_w<T>(lc, aA * inv_n, aA2 * inv_n, mC, wbp, wcp);
+      } else if constexpr (RES) {
+        float xC[NCH];
+        all_chains(wC[0], xC);
+        gather_w<T>(lc, wA, wA2, xC, wbp, wcp);
       } else {
         gather_w<T>(lc, wA, wA2, wC, wbp, wcp);
       }
     }
   }
   float wb[6], wc[CL];
-  gather_w<T>(lc, wA, wA2, wC, wb, wc);
+  if constexpr (RES) {
+    float xC[NCH];
+    all_chains(wC[0], xC);
+    gather_w<T>(lc, wA, wA2, xC, wb, wc);
+  } else {
+    gather_w<T>(lc, wA, wA2, wC, wb, wc);
+  }
   if (P.pos_iters <= 0) {
 #pragma unroll
     for (int b = 0; b < 6; ++b) wbp[b] = wb[b];
@@ -2187,6 +2301,17 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
     s.q[k] += h * nupc[k];
     s.qd[k] = nunc[k];
   }
+  // (RES) the impulses of the lane's own chain lc from their owner copy: an exchange every copy takes part in, though
+  // only copy 0 collects (a wave-uniform branch)
+  [[maybe_unused]] float lam_lc[RES ? CC : 1][3];
+  if constexpr (RES) {
+    if (__ballot(collect) != 0ull) {
+#pragma unroll
+      for (int j = 0; j < CC; ++j)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) lam_lc[j][i] = from_copy(lamc[0][j][i], lc);
+    }
+  }
   if (collect) {
     // (output addresses formed here: opaque_index)
     e = opaque_index(e);
@@ -2197,11 +2322,17 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
       for (int j = 0; j < CC; ++j) {
         if (T::T_ccb[j] == k) {
           float l0 = lamc[0][j][0], l1 = lamc[0][j][1], l2 = lamc[0][j][2];
+          if constexpr (RES) {
+            l0 = lam_lc[j][0];
+            l1 = lam_lc[j][1];
+            l2 = lam_lc[j][2];
+          } else {
 #pragma unroll
-          for (int c = 1; c < NCH; ++c) {
-            l0 = lc == c ? lamc[c][j][0] : l0;
-            l1 = lc == c ? lamc[c][j][1] : l1;
-            l2 = lc == c ? lamc[c][j][2] : l2;
+            for (int c = 1; c < NCH; ++c) {
+              l0 = lc == c ? lamc[c][j][0] : l0;
+              l1 = lc == c ? lamc[c][j][1] : l1;
+              l2 = lc == c ? lamc[c][j][2] : l2;
+            }
           }
           if constexpr (TERR) {  // f = (l0 n + l1 t1 + l2 t2) / h in the candidate's mesh frame
             float t1[3], t2[3];
@@ -2320,7 +2451,7 @@ __device__ __forceinline__ TeamLane team_lane(int N) {
   return t;
 }
 
-template <class T, bool TERR, bool TGS, int EPW, bool ROWL>
+template <class T, bool TERR, bool TGS, int EPW, bool ROWL, bool RES>
 __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(const DevModel* __restrict__ M, DevParams P,
                                                                  SimBuffers B, const float* __restrict__ tau_aos) {
   constexpr int LN = T::T_LANES, CL = T::T_CL, ND = T::ND;
@@ -2356,13 +2487,13 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(con
   GS_PROF_DECL
   for (int sstep = 0; sstep < P.substeps; ++sstep) {
     const bool last = (sstep == P.substeps - 1) && P.collect && tl.out;
-    substep_team<T, TERR, TGS, EPW, ROWL>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, nullptr, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
+    substep_team<T, TERR, TGS, EPW, ROWL, RES>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, nullptr, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
   }
   if (tl.out) team_store<T>(B.state, N, opaque_index(e), opaque_index(lc), s);
   GS_PROF_FLUSH
 }
 
-template <class T, bool TERR, bool TGS, int EPW, bool ROWL>
+template <class T, bool TERR, bool TGS, int EPW, bool ROWL, bool RES>
 __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(const DevModel* __restrict__ M, DevParams P,
                                                                 SimBuffers B, PdDev A) {
   constexpr int LN = T::T_LANES, CL = T::T_CL, ND = T::ND, NB = T::NB;
@@ -2411,10 +2542,12 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
         tau[k] = clampf(A.kp * (A.scale * aj + A.default_pos[lc * CL + k] - qj) - A.kd * qdj, -A.tlim, A.tlim);
       }
     }
-    const bool last = ((it % sub) == sub - 1) && P.collect && tl.out;
+    // contact forces once per launch: every collecting substep stores the same words of cf_soa, so only those of the
+    // launch's last substep survive it -- the earlier ones (four of five with one substep per simulate) are not formed
+    const bool last = it == total - 1 && P.collect && tl.out;
     GS_PROF(6)  // PD torque
     float* cf_aos = (it == total - 1) ? A.cf_out : nullptr;
-    substep_team<T, TERR, TGS, EPW, ROWL>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, cf_aos, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
+    substep_team<T, TERR, TGS, EPW, ROWL, RES>(M, mdl, P, s, tau, mu_t, N, e, lc, own, team, B.cf, last, cf_aos, shw_wave, sct, stash_tab + col GS_PROF_ARGS);
     if (it == n_pd - 1 && A.dof_out && tl.out) {
       const size_t d0 = dof0();
 #pragma unroll
@@ -2496,25 +2629,36 @@ static bool team_row_lanes(const DevParams& P, int epw) {
   if (kTeamBlock != GS_WAVE || epw != 4 || P.has_terrain) return false;
   return P.team_row_lanes >= 0 ? P.team_row_lanes != 0 : kTeamRowLanesPlane;
 }
+// Resident sweeps of a row-lane launch (the RES forms): DevParams::team_resident when the sim was created
+// with GS_TEAM_RESIDENT_SWEEPS set, else the default measured; never without row lanes
+constexpr bool kTeamResidentPlane = true;
+static bool team_resident_sweeps(const DevParams& P, int epw) {
+  if (!team_row_lanes(P, epw)) return false;
+  return P.team_resident >= 0 ? P.team_resident != 0 : kTeamResidentPlane;
+}
 void team_launch_form(const DevParams& P, int* epw, int* row_lanes) {
   *epw = team_epw(P, false);
   *row_lanes = team_row_lanes(P, *epw) ? 1 : 0;
 }
+int team_launch_resident(const DevParams& P) { return team_resident_sweeps(P, team_epw(P, false)) ? 1 : 0; }
 // the launch of kernel form K<T, TERR, TGS, EPW> chosen by the scene (TERR, TGS) and the envs per wave
 #define GS_TEAM_LAUNCH_EPW(K, EPW, ...)                                                                      \
   do {                                                                                                       \
     const dim3 g_((unsigned)blocks), b_((unsigned)WaveForm<EPW>::THREADS);                                   \
-    if (P.has_terrain && P.tgs) hipLaunchKernelGGL((K<T, true, true, EPW, false>), g_, b_, 0, st, __VA_ARGS__);  \
-    else if (P.has_terrain) hipLaunchKernelGGL((K<T, true, false, EPW, false>), g_, b_, 0, st, __VA_ARGS__); \
-    else if (P.tgs) hipLaunchKernelGGL((K<T, false, true, EPW, false>), g_, b_, 0, st, __VA_ARGS__);         \
-    else hipLaunchKernelGGL((K<T, false, false, EPW, false>), g_, b_, 0, st, __VA_ARGS__);                   \
+    if (P.has_terrain && P.tgs) hipLaunchKernelGGL((K<T, true, true, EPW, false, false>), g_, b_, 0, st, __VA_ARGS__);  \
+    else if (P.has_terrain) hipLaunchKernelGGL((K<T, true, false, EPW, false, false>), g_, b_, 0, st, __VA_ARGS__); \
+    else if (P.tgs) hipLaunchKernelGGL((K<T, false, true, EPW, false, false>), g_, b_, 0, st, __VA_ARGS__);         \
+    else hipLaunchKernelGGL((K<T, false, false, EPW, false, false>), g_, b_, 0, st, __VA_ARGS__);                   \
   } while (0)
 // the row-lane forms (plane, 4 envs per wave)
 #define GS_TEAM_LAUNCH_ROWL(K, ...)                                                                          \
   do {                                                                                                       \
     const dim3 g_((unsigned)blocks), b_((unsigned)WaveForm<4>::THREADS);                                     \
-    if (P.tgs) hipLaunchKernelGGL((K<T, false, true, 4, true>), g_, b_, 0, st, __VA_ARGS__);                 \
-    else hipLaunchKernelGGL((K<T, false, false, 4, true>), g_, b_, 0, st, __VA_ARGS__);                      \
+    const bool res_ = team_resident_sweeps(P, 4);                                                            \
+    if (P.tgs && res_) hipLaunchKernelGGL((K<T, false, true, 4, true, true>), g_, b_, 0, st, __VA_ARGS__);   \
+    else if (P.tgs) hipLaunchKernelGGL((K<T, false, true, 4, true, false>), g_, b_, 0, st, __VA_ARGS__);     \
+    else if (res_) hipLaunchKernelGGL((K<T, false, false, 4, true, true>), g_, b_, 0, st, __VA_ARGS__);      \
+    else hipLaunchKernelGGL((K<T, false, false, 4, true, false>), g_, b_, 0, st, __VA_ARGS__);               \
   } while (0)
 #define GS_TEAM_LAUNCH(K, epw, ...)                              \
   do {                                                           \

@@ -105,6 +105,7 @@ def lib():
             "gs_debug_terrain_query": (i, [vp, vp, vp, i, vp, vp]),
             "gs_debug_self_contacts": (i, [vp, i, vp, vp, vp]),
             "gs_debug_team_form": (i, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+            "gs_debug_team_sweeps": (i, [vp, C.POINTER(C.c_int)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -127,7 +128,7 @@ EXPORTED_SYMBOLS = [
     "gs_sim_set_force_sensors", "gs_sim_bind_force_sensors", "gs_sim_refresh_force_sensor",
     "gs_sim_add_triangle_mesh", "gs_debug_terrain_query", "gs_sim_refresh_rigid_body", "gs_sim_refresh_jacobian",
     "gs_sim_refresh_mass_matrix", "gs_sim_set_dof_drives", "gs_sim_bind_dof_targets", "gs_sim_set_self_collision",
-    "gs_debug_self_contacts", "gs_debug_team_form", "gs_sim_bind_dof_properties_env", "gs_sim_pd_tail_supported", "gs_sim_set_root_and_dof",
+    "gs_debug_self_contacts", "gs_debug_team_form", "gs_debug_team_sweeps", "gs_sim_bind_dof_properties_env", "gs_sim_pd_tail_supported", "gs_sim_set_root_and_dof",
 ]
 
 

@@ -6,8 +6,8 @@ Loads libgymsim_prof.so (-DGS_PHASE_PROFILE) instead of libgymsim.so, runs Anyma
 steps and prints, per kernel launch and wave, the s_memtime cycles of each solver phase and the
 number of contacts each wave executes in the PGS sweeps (wave-uniform control flow: a contact
 costs a wave its full latency if ANY of its envs has it active).  The sums are divided by the waves
-the launch's form really runs (gs_debug_team_form: 16, 8 or 4 envs per wave; GS_TEAM_ENVS_PER_WAVE and
-GS_TEAM_ROW_LANES choose the form as for any sim).
+the launch's form really runs (gs_debug_team_form: 16, 8 or 4 envs per wave; GS_TEAM_ENVS_PER_WAVE,
+GS_TEAM_ROW_LANES and GS_TEAM_RESIDENT_SWEEPS choose the form as for any sim).
 """
 import argparse
 import ctypes as C
