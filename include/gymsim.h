@@ -280,9 +280,11 @@ int gs_sim_set_self_collision(gs_sim *sim, int enable);
 
 /* Physics kernel selected by gs_sim_set_model: 1 one env per lane, 2 lane team, 3 host backend, 4 the
  * runtime-sized kernel (ABI 8: a topology with no compiled kernel -- any tree of revolute / prismatic joints with
- * plane contacts of sphere / capsule / cylinder / box candidates, joint limits, drives, per-actor dof properties;
- * one wave per env, dense joint-space rows; hull candidates, self-collision, terrain meshes and force sensors
- * need a compiled topology and are refused); -1 on error. */
+ * plane contacts of sphere / capsule / cylinder / box candidates and convex-hull manifolds, joint limits, drives,
+ * per-actor dof properties, self-collision from the model's pair table (gs_sim_set_self_collision), force
+ * sensors on leaf bodies (gs_sim_set_force_sensors) and gs_debug_self_contacts mode 0; one wave per env, dense
+ * joint-space rows; a terrain mesh needs a compiled topology and is refused, as is a model beyond a table limit,
+ * which the error names); -1 on error. */
 int gs_sim_kernel_variant(gs_sim *sim);
 
 /* Kernel time of the last gs_sim_pd_step / gs_sim_simulate launch measured with

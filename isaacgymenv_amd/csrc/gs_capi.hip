@@ -416,9 +416,16 @@ int gs_sim_add_triangle_mesh(gs_sim* s, const float* vertices, int64_t num_verti
 
 int gs_sim_set_model(gs_sim* s, const gs_model_desc* m) {
   if (!s || !m) return fail("gs_sim_set_model: null argument");
-  if (m->num_bodies > GS_MAXB || m->num_dofs > GS_MAXD || m->num_candidates > GS_MAXC || m->num_links > GS_MAXL ||
-      m->num_shapes > GS_MAXSH)
-    return fail("gs_sim_set_model: articulation exceeds compiled maxima (bodies/dofs/candidates/links)");
+  {  // table capacities of every kernel form (the runtime-sized kernel's tables are these too), each named
+    const struct { const char* what; int n, cap; } lim[] = {
+        {"bodies (32-bit ancestor masks)", m->num_bodies, GS_MAXB}, {"dofs", m->num_dofs, GS_MAXD},
+        {"contact candidates (3 rows each)", m->num_candidates, GS_MAXC}, {"links", m->num_links, GS_MAXL},
+        {"collision shapes", m->num_shapes, GS_MAXSH}};
+    for (const auto& l : lim)
+      if (l.n > l.cap)
+        return fail("%s", ("gs_sim_set_model: " + std::to_string(l.n) + " " + l.what + " exceed the limit of " +
+                           std::to_string(l.cap)).c_str());
+  }
   if (m->num_links < m->num_bodies || !m->link_body || !m->link_pose || !m->link_com ||
       (m->num_candidates > 0 && !m->cand_link))
     return fail("gs_sim_set_model: link tables missing (gs_model_desc ABI 2: num_links >= num_bodies)");
@@ -429,8 +436,10 @@ int gs_sim_set_model(gs_sim* s, const gs_model_desc* m) {
   const TopoEntry* t = find_topology(m);
   // A topology with no compiled kernel runs the runtime-sized kernel (gs_generic.hip, kernel_variant 4) on the GPU:
   // any tree of revolute / prismatic joints with plane contacts of point candidates (spheres, capsule / cylinder
-  // ends, box corners), joint limits and drives.  Hull candidates, self-collision, terrain meshes and force
-  // sensors need a compiled topology (tools/gen_topologies.py) and are refused where they are set up.
+  // ends, box corners) and convex-hull manifolds, joint limits and drives, self-collision of filter-0 actors from
+  // the model's pair table, force sensors on leaf bodies.  A terrain mesh needs a compiled topology
+  // (tools/gen_topologies.py), and the host backend has compiled topologies only; both are refused here.  So is a
+  // model beyond one of the kernel's tables, with the limit named.
   // (kernel_variant 4 asks for it on a compiled topology too: the cross-check of the two solver forms)
   const bool generic = !t || (s->params.kernel_variant == 4 && !s->host);
   if (generic) {
@@ -440,15 +449,28 @@ int gs_sim_set_model(gs_sim* s, const gs_model_desc* m) {
     if (s->params.kernel_variant == 1 || s->params.kernel_variant == 2)
       return fail("gs_sim_set_model: kernel_variant 1 / 2 requested but topology %s is not compiled (the runtime-"
                   "sized kernel is variant 4)", signature(m).c_str());
-    for (int c = 0; c < m->num_candidates; ++c)
-      if (m->cand_dyn && m->cand_dyn[c] >= 0)
-        return fail("gs_sim_set_model: topology %s has convex-hull candidates: the runtime-sized kernel has no hull "
-                    "ground manifold (compile the topology with tools/gen_topologies.py)", signature(m).c_str());
     if (s->dp.has_terrain)
       return fail("gs_sim_set_model: topology %s with a terrain mesh: the runtime-sized kernel has plane contacts only "
                   "(compile the topology with tools/gen_topologies.py)", signature(m).c_str());
     if (m->num_dofs + 6 > GS_MAXD + 6 || (m->num_candidates > 0 && !m->cand_shape))
       return fail("gs_sim_set_model: runtime-sized kernel tables missing for %s", signature(m).c_str());
+    // the kernel's table limits, each named (the general checks below repeat some for every kernel)
+    static_assert(GS_MAXB <= 32, "ancestor masks are 32-bit");
+    if (m->num_pairs > GS_MAXP)
+      return fail("%s", ("gs_sim_set_model: " + std::to_string(m->num_pairs) + " self-collision pairs exceed the "
+                         "runtime-sized kernel's limit of " + std::to_string(GS_MAXP) + " pairs (GS_MAXP)").c_str());
+    if (m->num_hull_verts > GS_MAXHV)
+      return fail("%s", ("gs_sim_set_model: " + std::to_string(m->num_hull_verts) + " hull vertices exceed the "
+                         "runtime-sized kernel's limit of " + std::to_string(GS_MAXHV) + " hull vertices (GS_MAXHV)")
+                            .c_str());
+    if (m->num_pairs > 0 && (m->pair_pool < 1 || m->pair_pool > GS_MAXPOOL))
+      return fail("%s", ("gs_sim_set_model: a self-contact pool of " + std::to_string(m->pair_pool) + " slots is "
+                         "outside the runtime-sized kernel's limit of 1.." + std::to_string(GS_MAXPOOL) +
+                         " slots (GS_MAXPOOL), 3 rows each").c_str());
+    for (int c = 0; c < m->num_candidates; ++c)
+      if (m->cand_dyn && m->cand_dyn[c] > 3)
+        return fail("gs_sim_set_model: hull slot %s of a candidate exceeds the runtime-sized kernel's limit of 4 "
+                    "ground contacts per hull", std::to_string(m->cand_dyn[c]).c_str());
   }
   if (!generic && m->num_pairs > 0 && m->pair_pool != t->npk)
     return fail("gs_sim_set_model: self-contact pool differs from the compiled topology's %s",
@@ -603,12 +625,17 @@ int gs_sim_set_model(gs_sim* s, const gs_model_desc* m) {
   int variant = 0;
   GenTopo hg;
   std::memset(&hg, 0, sizeof(hg));
+  int gen_feat = 0;
   if (generic) {
     hg.nc = m->num_candidates;
+    hg.ns = m->num_shapes;
+    hg.npool = m->num_pairs > 0 ? m->pair_pool : 0;
     for (int c = 0; c < m->num_candidates; ++c) {
       hg.cbody[c] = m->cand_body[c];
       hg.cshape[c] = m->cand_shape[c];
       hg.clink[c] = m->cand_link[c];
+      hg.cdyn[c] = m->cand_dyn[c] >= 0 ? m->cand_dyn[c] : -1;
+      gen_feat |= m->cand_dyn[c] >= 0 ? 1 : 0;
       if (hg.cbody[c] < 0 || hg.cbody[c] >= m->num_bodies || hg.cshape[c] < 0 || hg.cshape[c] >= m->num_shapes)
         return fail("gs_sim_set_model: candidate %s tables out of range", std::to_string(c).c_str());
     }
@@ -618,13 +645,15 @@ int gs_sim_set_model(gs_sim* s, const gs_model_desc* m) {
     g.name = "runtime-sized (gs_generic.hip)";
     g.sim = launch_sim_generic;
     g.pd = launch_pd_generic;
-    g.dbg_pool = nullptr;
+    g.dbg_pool = launch_dbg_pool_generic;
     g.nb = m->num_bodies; g.nd = m->num_dofs; g.nc = m->num_candidates; g.ns = m->num_shapes;
-    g.sens = 0;
-    g.row_floats = (int)generic_ws_floats(m->num_candidates, m->num_dofs, m->fixed_base);
+    g.sens = 1;
+    // rows of an env's workspace slice: limits, 3 per candidate, 3 per self-contact slot -- the most the kernel
+    // can build, so no env indexes past its slice
+    g.row_floats = (int)generic_ws_floats(m->num_candidates, m->num_dofs, m->fixed_base, hg.npool);
     g.row_lanes = 1;
-    g.npk = 0;
-    g.npair = 0;
+    g.npk = hg.npool;
+    g.npair = m->num_pairs;
     t = &g;
   }
   if (s->host) {
@@ -695,6 +724,7 @@ int gs_sim_set_model(gs_sim* s, const gs_model_desc* m) {
   s->dp.gen_links = generic ? s->d_links : nullptr;
   s->dp.gen_nd = m->num_dofs;
   s->dp.gen_nr = m->num_links;
+  s->dp.gen_feat = generic ? gen_feat : 0;
   return 0;
 }
 
@@ -921,8 +951,6 @@ int gs_sim_set_force_sensors(gs_sim* s, int n, const int32_t* bodies) {
   if (n < 0 || n > GS_MAXS || (n > 0 && !bodies)) return fail("gs_sim_set_force_sensors: at most 8 sensors");
   if (n > 0 && s->variant == 2)
     return fail("gs_sim_set_force_sensors: the lane-team kernel has no force sensors (use kernel_variant 1)");
-  if (n > 0 && s->variant == 4)
-    return fail("gs_sim_set_force_sensors: the runtime-sized kernel has no force sensors (compile the topology)");
   if (n > 0 && !s->topo->sens)
     return fail("gs_sim_set_force_sensors: topology %s is compiled without force sensors (sensors flag in "
                 "tools/gen_topologies.py MODELS)", s->topo->name);
@@ -937,6 +965,7 @@ int gs_sim_set_force_sensors(gs_sim* s, int n, const int32_t* bodies) {
     h.sens_of_body[b] = i;
   }
   h.nsens = n;
+  if (s->variant == 4) s->dp.gen_feat = (s->dp.gen_feat & ~2) | (n > 0 ? 2 : 0);
   if (s->host) return 0;
   hipError_t e = hipSetDevice(s->device);
   if (e == hipSuccess) e = hipMemcpy(s->d_model, &h, sizeof(DevModel), hipMemcpyHostToDevice);
@@ -999,9 +1028,6 @@ int gs_sim_set_self_collision(gs_sim* s, int enable) {
   if (!s || !s->topo) return fail("gs_sim_set_self_collision: model not set");
   if (enable && s->h_model.np > 0 && s->topo->npk <= 0)
     return fail("gs_sim_set_self_collision: the compiled topology has no self-contact pool");
-  if (enable && s->h_model.np > 0 && s->variant == 4)
-    return fail("gs_sim_set_self_collision: the runtime-sized kernel has no self-collision (compile the topology "
-                "with tools/gen_topologies.py, or create the actors with collision filter 1)");
   s->dp.self_collide = enable && s->h_model.np > 0;
   if (s->dp.self_collide && s->variant == 2 && !s->team_pairs) {  // this lane-team build has no pair rows
     if (s->params.kernel_variant == 2)

@@ -18,12 +18,27 @@
 // by a ballot prefix in candidate order), Jacobian rows (lane = column), the row solves (lane = row) and the
 // Gauss-Seidel sweeps (lane = velocity component: u = J v is a wave reduction, v += W dl a vector update).  The
 // rows J, W live in a per-env workspace in device memory (SimBuffers::rows), the factor and the body tables in
-// LDS.  Not supported here (fails loudly at set-up): hull candidates, self-collision, terrain meshes, force
-// sensors -- those robots need a compiled topology.
+// LDS.
+//
+// Two forms of the kernel, chosen per launch (launch_sim_generic).  The plain form is the above and nothing else.
+// The full form (FEAT) adds, for sims that have them:
+//  * convex-hull ground manifolds: per hull shape near the ground, the 4-point selection of
+//    gs_pairs.h hull_ground_select with lane = vertex in rounds of 64 and (value, index) wave reductions whose ties
+//    go to the lowest index; the selected body-frame points stay in LDS and stand in for M->cpoint;
+//  * self-collision: shape world data in LDS (lane = shape), broadphase with lane = pair and a
+//    ballot prefix into pair order, narrowphase with one listed pair per lane (gs_pairs.h self_pair, unchanged),
+//    at most npool contacts in pair order; their rows (J = d . (v_A(x) - v_B(x)), common ancestors cancel) follow
+//    the ground rows and are solved in the same sweeps; a row below GS_MIN_RESPONSE takes no impulse;
+//  * force sensors on leaf bodies, lane = body, from the last substep's accelerations.
+// Not supported here (fails loudly at set-up): terrain meshes -- those robots need a compiled topology -- and no
+// host backend.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "gs_internal.h"
 #include "gs_math.h"
+#include "gs_pairs.h"
 
 namespace {
 
@@ -35,10 +50,187 @@ struct GBody {  // LDS body tables of one env
   SpI Ib[GS_MAXB], Ic[GS_MAXB];
 };
 
+// Row tables: limit rows (<= nd), 3 rows per ground candidate, and in the full form 3 rows per self-contact slot
+template <bool FEAT>
+constexpr int kGRows = 3 * GS_MAXC + GS_MAXD + (FEAT ? 3 * GS_MAXPOOL : 0);
+
+// LDS of the full form (FEAT): hull manifolds, shape world data, the near-pair list and the self-contact pool
+constexpr int kGPE = kPoolLB + 1;  // pool entry: gs_pairs.h layout up to the links (x n t1 t2 sep mu bodies links)
+struct GFeat {
+  float shw[kShW * GS_MAXSH];    // shape world data (gs_pairs.h layout, stride 1)
+  float hp[4 * GS_MAXSH][3];     // a hull shape's selected ground vertices, body frame (slot 4 sh + j)
+  int hn[GS_MAXSH];              // how many of them (0: not a hull, or clear of the ground)
+  float pool[GS_MAXPOOL * kGPE];
+  int near[GS_MAXP];             // pairs within reach of the broadphase, in pair order
+};
+struct GNoFeat {};
+
+// self_pair's topology parameter for a runtime pair table: shape kinds from the model, the pool cap applied by the
+// caller (a lane's pair yields at most 2 contacts)
+struct GenPairT {
+  static constexpr int NPK = GS_MAXPOOL;
+};
+
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, kGW);
   return x;
+}
+
+// (value, index) maximum over the wave: the largest value, on ties the lowest index (-1 = none loses every tie) --
+// what a serial scan in index order with a strict > keeps
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, kGW);
+    const int oi = __shfl_xor(i, o, kGW);
+    if (ov > v || (ov == v && (unsigned)oi < (unsigned)i)) { v = ov; i = oi; }
+  }
+}
+
+// gs_pairs.h hull_ground_select spread over the wave: lane = vertex, in rounds of 64 over the hull's range; every
+// step is a (value, index) reduction with the serial rule's tie-break (first index).  Returns the count (uniform),
+// the vertex indices in sel.
+__device__ int hull_select_wave(const DevModel* __restrict__ M, int sh, const float* R, const float* X, float rootz,
+                                float off, int* sel, int lane) {
+  const int v0 = M->hv0[sh], v1 = M->hv1[sh];
+  auto world = [&](const float* v, float* w) {
+    w[0] = X[0] + R[0] * v[0] + R[1] * v[1] + R[2] * v[2];
+    w[1] = X[1] + R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
+    w[2] = rootz + X[2] + R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
+  };
+  // best over the vertices of f(w) (a value to maximise; `all`: vertices at or above `off` count too) above floor
+  auto scan = [&](float floor, bool all, auto&& f, int& idx) {
+    float best = floor;
+    int bi = -1;
+    for (int k = v0 + lane; k < v1; k += kGW) {
+      const float4 hv = *reinterpret_cast<const float4*>(M->hv[k]);
+      const float v[3] = {hv.x, hv.y, hv.z};
+      float w[3];
+      world(v, w);
+      if (!all && !(w[2] < off)) continue;
+      const float val = f(w);
+      if (val > best) { best = val; bi = k; }
+    }
+    wave_argmax(best, bi);
+    idx = bi;
+    return best;
+  };
+  int i0, i1, i2, i3;
+  const float nz = scan(-3.0e38f, true, [&](const float* w) { return -w[2]; }, i0);
+  if (i0 < 0 || !(-nz < off)) return 0;
+  int n = 0;
+  float p0[3];
+  world(M->hv[i0], p0);
+  sel[n++] = i0;
+  scan(1e-10f, false, [&](const float* w) {
+    return (w[0] - p0[0]) * (w[0] - p0[0]) + (w[1] - p0[1]) * (w[1] - p0[1]);
+  }, i1);
+  if (i1 < 0) return n;
+  float p1[3];
+  world(M->hv[i1], p1);
+  sel[n++] = i1;
+  const float ex = p1[0] - p0[0], ey = p1[1] - p0[1];
+  scan(1e-10f, false, [&](const float* w) { return fabsf(ex * (w[1] - p0[1]) - ey * (w[0] - p0[0])); }, i2);
+  if (i2 < 0) return n;
+  float p2[3];
+  world(M->hv[i2], p2);
+  sel[n++] = i2;
+  const float sg = (ex * (p2[1] - p0[1]) - ey * (p2[0] - p0[0])) > 0.f ? 1.f : -1.f;
+  scan(1e-10f, false, [&](const float* w) {
+    const float e0 = sg * ((p1[0] - p0[0]) * (w[1] - p0[1]) - (p1[1] - p0[1]) * (w[0] - p0[0]));
+    const float e1 = sg * ((p2[0] - p1[0]) * (w[1] - p1[1]) - (p2[1] - p1[1]) * (w[0] - p1[0]));
+    const float e2 = sg * ((p0[0] - p2[0]) * (w[1] - p2[1]) - (p0[1] - p2[1]) * (w[0] - p2[0]));
+    return -fminf(fminf(e0, e1), e2);
+  }, i3);
+  if (i3 >= 0) sel[n++] = i3;
+  return n;
+}
+
+// Ground manifolds of the hull shapes from the body poses in B: a hull whose bounding sphere clears
+// contact_offset has none; the selected vertices' body-frame points go to X.hp, their count to X.hn.
+__device__ void hull_manifolds(const DevModel* __restrict__ M, const GenTopo* __restrict__ G, const DevParams& P,
+                               const GBody& B, float rootz, GFeat& X, int lane) {
+  for (int sh = 0; sh < G->ns; ++sh) {
+    int n = 0, sel[4] = {0, 0, 0, 0};
+    if (M->shkind[sh] == 4 && P.has_ground) {
+      const int b = M->shbody[sh];
+      const float* R = B.R[b];
+      const float* sc = M->shc[sh];
+      const float cz = rootz + B.P[b][2] + R[6] * sc[0] + R[7] * sc[1] + R[8] * sc[2];
+      if (cz - sc[3] < P.contact_offset) n = hull_select_wave(M, sh, R, B.P[b], rootz, P.contact_offset, sel, lane);
+    }
+    if (lane < n) {
+      const int k = lane == 0 ? sel[0] : (lane == 1 ? sel[1] : (lane == 2 ? sel[2] : sel[3]));
+      for (int a = 0; a < 3; ++a) X.hp[4 * sh + lane][a] = M->hv[k][a];
+    }
+    if (lane == 0) X.hn[sh] = n;
+  }
+  __syncthreads();
+}
+
+// Self-contacts of the env from the body poses in B, as gs_pairs.h self_contacts finds them, spread
+// over the wave: shape world data (lane = shape), broadphase (lane = pair, 64 per round, the near ones ranked by a
+// ballot prefix into pair order), narrowphase (one listed pair per lane: gs_pairs.h self_pair), and the contacts
+// ranked again into the pool -- at most npool, in pair order, later ones dropped.  Returns the count (uniform).
+__device__ int self_contacts_wave(const DevModel* __restrict__ M, const GenTopo* __restrict__ G, const DevParams& P,
+                                  const float* __restrict__ mu, int N, int e, const GBody& B, GFeat& X, int lane) {
+  for (int sh = lane; sh < G->ns; sh += kGW) {
+    const int b = M->shbody[sh];
+    float* o = X.shw + kShW * sh;
+    float Rs[9], t[3];
+    mat3mul(B.R[b], M->shR[sh], Rs);
+    for (int k = 0; k < 9; ++k) o[k] = Rs[k];
+    mat3vec(B.R[b], M->sht[sh], t);
+    for (int k = 0; k < 3; ++k) o[9 + k] = B.P[b][k] + t[k];
+    mat3vec(B.R[b], M->shc[sh], t);
+    for (int k = 0; k < 3; ++k) o[12 + k] = B.P[b][k] + t[k];
+  }
+  __syncthreads();
+  const int np = M->np, npool = G->npool;
+  const float off = P.contact_offset;
+  const ShapeConstsM sc{M};
+  int cnt = 0;
+  for (int q0 = 0; q0 < np; q0 += kGW) {
+    const int q = q0 + lane;
+    bool near = false;
+    if (q < np) {
+      const int a = M->pa[q], b = M->pb[q];
+      const float* sa = X.shw + kShW * a + 12;
+      const float* sb = X.shw + kShW * b + 12;
+      const float d[3] = {sa[0] - sb[0], sa[1] - sb[1], sa[2] - sb[2]};
+      const float rr = sc.brad(a) + sc.brad(b) + off;
+      near = dot3f(d, d) < rr * rr;
+    }
+    const unsigned long long bal = __ballot(near);
+    if (near) X.near[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = q;
+    cnt += __popcll(bal);
+  }
+  __syncthreads();
+  int n = 0;
+  for (int i0 = 0; i0 < cnt && n < npool; i0 += kGW) {
+    const int i = i0 + lane;
+    int c = 0, a = 0, b = 0;
+    float rec[2 * kRec];
+    if (i < cnt) {
+      const int q = X.near[i];
+      a = M->pa[q];
+      b = M->pb[q];
+      self_pair<GenPairT, 1, 1, kRec, ShapeConstsM, true>(M, sc, P, mu, N, e, X.shw, rec, a, b, M->pk[q], c);
+    }
+    const unsigned long long b1 = __ballot(c >= 1), b2 = __ballot(c >= 2), lower = (1ull << lane) - 1ull;
+    const int slot = n + __popcll(b1 & lower) + __popcll(b2 & lower);
+    for (int j = 0; j < c; ++j) {
+      if (slot + j >= npool) break;
+      float* o = X.pool + kGPE * (slot + j);
+      for (int k = 0; k < 6; ++k) o[k] = rec[kRec * j + k];
+      o[kPoolSep] = rec[kRec * j + kRecSep];
+      pool_entry_finish<1>(M, mu, N, e, a, b, o);
+    }
+    n += __popcll(b1) + __popcll(b2);
+  }
+  __syncthreads();
+  return n < npool ? n : npool;
 }
 
 __device__ __forceinline__ void axis_rot(const float* a, float q, float* Rq) {
@@ -57,16 +249,21 @@ __device__ __forceinline__ float gdofp(const DevParams& P, int nd, int e, int f,
 
 // One substep of env e (the whole wave).  st: SoA state; tau: [N][nd] or null; ws: this env's row workspace
 // (J then W, row stride nv); cf: [3 nr][N] or null (collect).
+// FEAT: the full form -- hull ground manifolds, self-contacts and force sensors (sens: [6 nsens][N] or null); X is
+// its LDS.  Without FEAT none of that code exists: a robot of point candidates with neither pairs nor sensors runs
+// the plain form (launch_sim_generic selects).
+template <bool FEAT>
 __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* __restrict__ L,
                                 const GenTopo* __restrict__ G, const DevParams& P, float* __restrict__ st,
                                 const float* __restrict__ mu, int N, int e, const float* __restrict__ tau_e,
-                                float* __restrict__ ws, float* __restrict__ cf, GBody& B, float* Ml, float* rowf,
-                                int* rowi, float* vec) {
+                                float* __restrict__ ws, float* __restrict__ cf, float* __restrict__ sens, GBody& B,
+                                float* Ml, float* rowf, int* rowi, float* vec,
+                                std::conditional_t<FEAT, GFeat, GNoFeat>& X) {
   const int lane = threadIdx.x & (kGW - 1);
   const int nb = L->nb, nd = L->nd, fb = L->fixed_base;
   const int nbase = fb ? 0 : 6, nv = nbase + nd;
   const float h = P.h;
-  const int maxrows = 3 * G->nc + nd;
+  const int maxrows = 3 * G->nc + nd + 3 * G->npool;
   float* Jw = ws;                             // [maxrows][nv]
   float* Ww = ws + (size_t)maxrows * nv;      // [maxrows][nv]
   // vec: nu (nv) | nuf (nv) | rhs (nv) | root (13) | q (nd) | qd (nd) | dforce (nd) | dimpl (nd)
@@ -80,10 +277,11 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
   float* dimpl = dforce + GS_MAXD;
   // row tables (rowf: separation, mu, normal xyz, Dr, lam | rowi: kind (0 limit, 1 contact row), candidate / dof)
   float* rsep = rowf;
-  float* rmu = rowf + 1 * (3 * GS_MAXC + GS_MAXD);
-  float* rD = rowf + 2 * (3 * GS_MAXC + GS_MAXD);
-  float* rlam = rowf + 3 * (3 * GS_MAXC + GS_MAXD);
-  float* rsg = rowf + 4 * (3 * GS_MAXC + GS_MAXD);  // limit rows: +1 lower, -1 upper
+  constexpr int NR = kGRows<FEAT>;
+  float* rmu = rowf + 1 * NR;
+  float* rD = rowf + 2 * NR;
+  float* rlam = rowf + 3 * NR;
+  float* rsg = rowf + 4 * NR;  // limit rows: +1 lower, -1 upper
 
   // ---------------- state in
   if (lane < 13) root[lane] = st[(size_t)lane * N + e];
@@ -179,6 +377,13 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     for (int j = 0; j < nd; ++j) nu[nbase + j] = qd[j];
   }
   __syncthreads();
+
+  // ---------------- full form: hull ground manifolds and the self-contact pool from the body poses
+  int npc = 0;
+  if constexpr (FEAT) {
+    if (P.gen_feat & 1) hull_manifolds(M, G, P, B, root[2], X, lane);
+    if (P.self_collide) npc = self_contacts_wave(M, G, P, mu, N, e, B, X, lane);
+  }
 
   // ---------------- drives and generalized forces (lane = dof)
   for (int j = lane; j < nd; j += kGW) {
@@ -305,6 +510,19 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     }
     nlim = __popcll(bal);
   }
+  // (full form) candidate c's body-frame point: a hull slot reads its manifold vertex; false = no such vertex
+  auto cand_point = [&](int c, float* pt) {
+    if constexpr (FEAT) {
+      const int dy = G->cdyn[c];
+      if (dy >= 0) {
+        const int sh = G->cshape[c];
+        for (int k = 0; k < 3; ++k) pt[k] = X.hp[4 * sh + (dy & 3)][k];
+        return dy < X.hn[sh];
+      }
+    }
+    for (int k = 0; k < 3; ++k) pt[k] = M->cpoint[c][k];
+    return true;
+  };
   int nrows = nlim;
   for (int c0 = 0; c0 < G->nc; c0 += kGW) {
     const int c = c0 + lane;
@@ -313,9 +531,17 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     if (c < G->nc && P.has_ground) {
       const int b = G->cbody[c];
       float x[3];
-      mat3vec(B.R[b], M->cpoint[c], x);
-      dist = root[2] + B.P[b][2] + x[2] - M->cradius[c];
-      act = dist < P.contact_offset;
+      if constexpr (FEAT) {  // a hull slot's point is the manifold's vertex, absent beyond the manifold's count
+        float pt[3];
+        const bool have = cand_point(c, pt);
+        mat3vec(B.R[b], pt, x);
+        dist = root[2] + B.P[b][2] + x[2] - M->cradius[c];
+        act = have && dist < P.contact_offset;
+      } else {
+        mat3vec(B.R[b], M->cpoint[c], x);
+        dist = root[2] + B.P[b][2] + x[2] - M->cradius[c];
+        act = dist < P.contact_offset;
+      }
     }
     const unsigned long long bal = __ballot(act);
     const int slot = nrows + 3 * __popcll(bal & ((1ull << lane) - 1ull));
@@ -330,6 +556,18 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     }
     nrows += 3 * __popcll(bal);
   }
+  const int nground = nrows;  // rows [nlim, nground): ground contacts; [nground, nrows): self-contacts
+  if constexpr (FEAT) {
+    // self-contact rows after the ground rows, pool order: normal, tangent 1, tangent 2 (id = nc + pool slot)
+    for (int t = lane; t < 3 * npc; t += kGW) {
+      const int p = t / 3;
+      rowi[2 * (nrows + t)] = 1 + (t - 3 * p);
+      rowi[2 * (nrows + t) + 1] = G->nc + p;
+      rsep[nrows + t] = X.pool[kGPE * p + kPoolSep];
+      rmu[nrows + t] = X.pool[kGPE * p + kPoolMu];
+    }
+    nrows += 3 * npc;
+  }
   __syncthreads();
   // Jacobian rows (lane = column k): a limit row is +-e_dof; a contact row's direction d (normal z, tangents x, y
   // for the plane) times the velocity of the contact point xc = x - r n over the candidate body's path
@@ -340,10 +578,34 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
       float v = 0.f;
       if (kind == 0) {
         v = k == nbase + id ? rsg[r] : 0.f;
+      } else if (FEAT && r >= nground) {
+        // self-contact: d . (v_A(x) - v_B(x)) -- S_i's velocity at x where body i is on A's path, minus it on B's
+        // (a common ancestor's column and the base columns cancel)
+        if constexpr (FEAT) {
+          const float* o = X.pool + kGPE * (id - G->nc);
+          if (k >= nbase) {
+            const int i = L->dbody[k - nbase];
+            const int ba = (int)o[kPoolBA], bb = (int)o[kPoolBB];
+            const float coef = (float)((L->anc_mask[ba] >> i) & 1u) - (float)((L->anc_mask[bb] >> i) & 1u);
+            if (coef != 0.f) {
+              const float* d = o + (kind == 1 ? kPoolN : (kind == 2 ? kPoolT1 : kPoolT2));
+              float vx[3];
+              cross3(B.S[i], o + kPoolX, vx);
+              for (int a = 0; a < 3; ++a) vx[a] += B.S[i][3 + a];
+              v = coef * dot3f(d, vx);
+            }
+          }
+        }
       } else {
         const int b = G->cbody[id];
         float x[3];
-        mat3vec(B.R[b], M->cpoint[id], x);
+        if constexpr (FEAT) {
+          float pt[3];
+          cand_point(id, pt);
+          mat3vec(B.R[b], pt, x);
+        } else {
+          mat3vec(B.R[b], M->cpoint[id], x);
+        }
         const float xc[3] = {B.P[b][0] + x[0], B.P[b][1] + x[1], B.P[b][2] + x[2] - M->cradius[id]};
         const int ax = kind == 1 ? 2 : (kind == 2 ? 0 : 1);  // normal z, tangent 1 x, tangent 2 y
         if (k < nbase) {
@@ -375,6 +637,9 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     chol_solve(Jr, Wr, 1);
     float d = 0.f;
     for (int k = 0; k < nv; ++k) d += Jr[k] * Wr[k];
+    if constexpr (FEAT) {
+      if (r >= nground && !(d > GS_MIN_RESPONSE)) d = 0.f;  // a self-contact row no dof can separate: no impulse
+    }
     rD[r] = d;
     rlam[r] = 0.f;
   }
@@ -425,6 +690,66 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     const float vm = gdofp(P, nd, e, 5, j, M->vmax[j]);
     if (vm > 0.f) { v = clampf(v, -vm, vm); vpos = clampf(vpos, -vm, vm); }
   }
+  // ---------------- full form: force sensors on leaf bodies (gs_solver.h's T::SENS block), lane =
+  // body.  The wrench through the parent joint, f = I_b a_b + v_b x* I_b v_b - f_contact, with a_b = A_b (velocity
+  // products + gravity, already in B.F) + the base's acceleration + sum over the path of S_k qdd_k, qdd = (nu_new -
+  // nu) / h; a leaf's B.F / B.Ic are still its own RNEA force / inertia.  About the body origin, in body axes.
+  if constexpr (FEAT) {
+    if (sens && M->nsens > 0) {
+      const float inv_h = 1.f / h;
+      if (lane < nv) rhs[lane] = (v - nu[lane]) * inv_h;  // (rhs is free after the free velocity)
+      __syncthreads();
+      const int b = lane;
+      const int si = (b > 0 && b < nb) ? M->sens_of_body[b] : -1;
+      if (si >= 0) {
+        float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (!fb) {
+          float wxp[3];
+          cross3(&nu[0], &nu[3], wxp);
+          for (int k = 0; k < 3; ++k) { a[k] = rhs[k]; a[3 + k] = rhs[3 + k] - wxp[k]; }
+        }
+        for (int kk = 1; kk < nb; ++kk)
+          if ((L->anc_mask[b] >> kk) & 1u) {
+            const float qdd = rhs[nbase + L->bdof[kk]];
+            for (int k = 0; k < 6; ++k) a[k] += B.S[kk][k] * qdd;
+          }
+        float ia[6], f[6];
+        spi_mul(B.Ic[b], a, ia);
+        for (int k = 0; k < 6; ++k) f[k] = B.F[b][k] + ia[k];
+        for (int r = nlim; r < nground; r += 3) {
+          const int c = rowi[2 * r + 1];
+          if (G->cbody[c] != b) continue;
+          float pt[3], x[3], n3[3];
+          cand_point(c, pt);
+          mat3vec(B.R[b], pt, x);
+          x[0] += B.P[b][0]; x[1] += B.P[b][1]; x[2] += B.P[b][2] - M->cradius[c];
+          const float fc[3] = {rlam[r + 1] * inv_h, rlam[r + 2] * inv_h, rlam[r] * inv_h};
+          cross3(x, fc, n3);
+          for (int k = 0; k < 3; ++k) { f[k] -= n3[k]; f[3 + k] -= fc[k]; }
+        }
+        for (int r = nground; r < nrows; r += 3) {
+          const float* o = X.pool + kGPE * (rowi[2 * r + 1] - G->nc);
+          const int ba = (int)o[kPoolBA], bb = (int)o[kPoolBB];
+          if (ba != b && bb != b) continue;
+          const float sg = ba == b ? inv_h : -inv_h;
+          float fc[3], n3[3];
+          for (int k = 0; k < 3; ++k)
+            fc[k] = sg * (rlam[r] * o[kPoolN + k] + rlam[r + 1] * o[kPoolT1 + k] + rlam[r + 2] * o[kPoolT2 + k]);
+          cross3(o + kPoolX, fc, n3);
+          for (int k = 0; k < 3; ++k) { f[k] -= n3[k]; f[3 + k] -= fc[k]; }
+        }
+        float xf[3], tq[3];
+        cross3(B.P[b], &f[3], xf);
+        for (int k = 0; k < 3; ++k) tq[k] = f[k] - xf[k];
+        const float* Rb = B.R[b];
+        for (int k = 0; k < 3; ++k) {
+          sens[(size_t)(6 * si + k) * N + e] = Rb[k] * f[3] + Rb[3 + k] * f[4] + Rb[6 + k] * f[5];
+          sens[(size_t)(6 * si + 3 + k) * N + e] = Rb[k] * tq[0] + Rb[3 + k] * tq[1] + Rb[6 + k] * tq[2];
+        }
+      }
+      __syncthreads();
+    }
+  }
   // ---------------- integrate and store
   if (lane < nv) { nu[lane] = v; nuf[lane] = vpos; }  // (nu: new velocity, nuf: position-phase velocity)
   __syncthreads();
@@ -456,11 +781,21 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
   if (cf) {
     for (int l = lane; l < L->nr; l += kGW) {
       float f[3] = {0.f, 0.f, 0.f};
-      for (int r = nlim; r < nrows; r += 3) {
+      for (int r = nlim; r < nground; r += 3) {
         if (G->clink[rowi[2 * r + 1]] != l) continue;
         f[0] += rlam[r + 1] / h;
         f[1] += rlam[r + 2] / h;
         f[2] += rlam[r] / h;
+      }
+      if constexpr (FEAT) {  // a self-contact's force: + on link A, - on link B
+        for (int r = nground; r < nrows; r += 3) {
+          const float* o = X.pool + kGPE * (rowi[2 * r + 1] - G->nc);
+          const int la = (int)o[kPoolLA], lb = (int)o[kPoolLB];
+          if (la != l && lb != l) continue;
+          const float sg = la == l ? 1.f : -1.f;
+          for (int k = 0; k < 3; ++k)
+            f[k] += sg * ((rlam[r] * o[kPoolN + k] + rlam[r + 1] * o[kPoolT1 + k] + rlam[r + 2] * o[kPoolT2 + k]) / h);
+        }
       }
       for (int k = 0; k < 3; ++k) cf[(size_t)(3 * l + k) * N + e] = f[k];
     }
@@ -468,25 +803,84 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
   __syncthreads();
 }
 
+constexpr int kGVec = 3 * kGMaxV + 13 + 4 * GS_MAXD;
+template <bool FEAT>
+constexpr size_t kGLds = sizeof(GBody) + sizeof(float) * (kGMaxV * kGMaxV + 5 * kGRows<FEAT> + kGVec) +
+                         sizeof(int) * 2 * kGRows<FEAT> + (FEAT ? sizeof(GFeat) : 0);
+static_assert(kGLds<true> <= 160 * 1024 && kGLds<false> <= 160 * 1024, "static LDS beyond a CU's 160 KB");
+
+template <bool FEAT>
 __global__ __launch_bounds__(kGW) void k_simulate_generic(const DevModel* __restrict__ M, DevParams P, SimBuffers Bf,
                                                           const float* __restrict__ tau) {
   __shared__ GBody B;
   __shared__ float Ml[kGMaxV * kGMaxV];
-  __shared__ float rowf[5 * (3 * GS_MAXC + GS_MAXD)];
-  __shared__ int rowi[2 * (3 * GS_MAXC + GS_MAXD)];
-  __shared__ float vec[3 * kGMaxV + 13 + 4 * GS_MAXD];
+  __shared__ float rowf[5 * kGRows<FEAT>];
+  __shared__ int rowi[2 * kGRows<FEAT>];
+  __shared__ float vec[kGVec];
+  __shared__ std::conditional_t<FEAT, GFeat, GNoFeat> X;
   const int e = blockIdx.x;
   if (e >= Bf.N) return;
   const DevLinks* L = P.gen_links;
   const GenTopo* G = P.gen;
   const int nv = (L->fixed_base ? 0 : 6) + L->nd;
-  const size_t ws_per_env = (size_t)2 * (3 * G->nc + L->nd) * nv;
+  const size_t ws_per_env = (size_t)2 * (3 * G->nc + L->nd + 3 * G->npool) * nv;  // generic_ws_floats
   float* ws = Bf.rows + ws_per_env * e;
   for (int s = 0; s < P.substeps; ++s) {
     const bool last = s == P.substeps - 1;
-    generic_substep(M, L, G, P, Bf.state, Bf.mu, Bf.N, e, tau ? tau + (size_t)e * L->nd : nullptr, ws,
-                    (last && P.collect) ? Bf.cf : nullptr, B, Ml, rowf, rowi, vec);
+    generic_substep<FEAT>(M, L, G, P, Bf.state, Bf.mu, Bf.N, e, tau ? tau + (size_t)e * L->nd : nullptr, ws,
+                          (last && P.collect) ? Bf.cf : nullptr, last ? Bf.sens : nullptr, B, Ml, rowf, rowi, vec, X);
   }
+}
+
+// gs_debug_self_contacts on the runtime-sized kernel: the pool self_contacts_wave finds from the current state,
+// out [N][npool][10] = x (3) n (3) separation friction body a body b, count [N] (gs_physics_impl.h k_dbg_pool)
+__global__ __launch_bounds__(kGW) void k_dbg_pool_generic(const DevModel* __restrict__ M, DevParams P, SimBuffers Bf,
+                                                          float* __restrict__ out, int* __restrict__ count) {
+  __shared__ GBody B;
+  __shared__ GFeat X;
+  __shared__ float qs[13 + GS_MAXD];
+  const int e = blockIdx.x, lane = threadIdx.x, N = Bf.N;
+  if (e >= N) return;
+  const DevLinks* L = P.gen_links;
+  const GenTopo* G = P.gen;
+  const int nb = L->nb, nd = L->nd;
+  if (lane < 13) qs[lane] = Bf.state[(size_t)lane * N + e];
+  for (int j = lane; j < nd; j += kGW) qs[13 + j] = Bf.state[(size_t)(13 + j) * N + e];
+  __syncthreads();
+  if (lane == 0) {  // body poses as generic_substep forms them
+    const float* root = qs;
+    const float qn = 1.f / sqrtf(root[3] * root[3] + root[4] * root[4] + root[5] * root[5] + root[6] * root[6]);
+    const float q4[4] = {root[3] * qn, root[4] * qn, root[5] * qn, root[6] * qn};
+    quat_to_mat(q4, B.R[0]);
+    B.P[0][0] = B.P[0][1] = B.P[0][2] = 0.f;
+    for (int i = 1; i < nb; ++i) {
+      const int pa = L->parent[i];
+      float RJ[9], t[3], aw[3];
+      mat3mul(B.R[pa], M->jR[i], RJ);
+      mat3vec(B.R[pa], M->jt[i], t);
+      for (int k = 0; k < 3; ++k) B.P[i][k] = B.P[pa][k] + t[k];
+      mat3vec(RJ, M->jaxis[i], aw);
+      const float qj = qs[13 + L->bdof[i]];
+      if (L->jkind[i] == 1) {
+        float Rq[9];
+        axis_rot(M->jaxis[i], qj, Rq);
+        mat3mul(RJ, Rq, B.R[i]);
+      } else {
+        for (int k = 0; k < 9; ++k) B.R[i][k] = RJ[k];
+        for (int k = 0; k < 3; ++k) B.P[i][k] += aw[k] * qj;
+      }
+    }
+  }
+  __syncthreads();
+  const int n = self_contacts_wave(M, G, P, Bf.mu, N, e, B, X, lane);
+  const int npk = G->npool > 0 ? G->npool : 1;
+  for (int t = lane; t < n * 10; t += kGW) {
+    const int p = t / 10, k = t - 10 * p;
+    const int src = k < 6 ? k : kPoolSep + (k - 6);  // x, n | separation, friction, body a, body b: contiguous
+    static_assert(kPoolMu == kPoolSep + 1 && kPoolBA == kPoolSep + 2 && kPoolBB == kPoolSep + 3, "pool entry layout");
+    out[((size_t)e * npk + p) * 10 + k] = X.pool[kGPE * p + src];
+  }
+  if (lane == 0) count[e] = n;
 }
 
 __global__ void k_generic_pd_torque(const DevParams P, SimBuffers Bf, PdDev A, int nd, int first, float* tau) {
@@ -505,10 +899,25 @@ __global__ void k_generic_pd_torque(const DevParams P, SimBuffers Bf, PdDev A, i
 hipError_t launch_sim_generic(const DevModel* M, const DevParams& P, const SimBuffers& B, const float* tau,
                               hipStream_t st) {
   if (!P.gen || !P.gen_links || !B.rows) return hipErrorInvalidValue;
-  if (P.has_terrain || P.self_collide) return hipErrorNotSupported;
+  if (P.has_terrain) return hipErrorNotSupported;
   if (B.N <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_simulate_generic, dim3(B.N), dim3(kGW), 0, st, M, P, B, tau);
+  // the full form only where the sim has a hull candidate, a force sensor or self-collision: every other robot runs
+  // the plain form, which carries none of their code, registers or LDS
+  if (P.gen_feat || P.self_collide)
+    hipLaunchKernelGGL(k_simulate_generic<true>, dim3(B.N), dim3(kGW), 0, st, M, P, B, tau);
+  else
+    hipLaunchKernelGGL(k_simulate_generic<false>, dim3(B.N), dim3(kGW), 0, st, M, P, B, tau);
   return hipGetLastError();
+}
+
+hipError_t launch_dbg_pool_generic(const DevModel* M, const DevParams& P, const SimBuffers& B, int mode, float* out,
+                                   int* count, hipStream_t st) {
+  if (mode != 0 || !P.gen || !P.gen_links) return hipErrorInvalidValue;
+  if (B.N <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dbg_pool_generic, dim3(B.N), dim3(kGW), 0, st, M, P, B, out, count);
+  const hipError_t e = hipGetLastError();
+  const hipError_t e2 = hipStreamSynchronize(st);
+  return e != hipSuccess ? e : e2;
 }
 
 // The fused PD decimation step on the generic kernel: per decimation step one PD-torque launch (into

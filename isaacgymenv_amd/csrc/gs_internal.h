@@ -93,6 +93,8 @@ struct DevParams {
   const struct GenTopo* gen;
   const struct DevLinks* gen_links;
   int gen_nd, gen_nr;
+  int gen_feat;          // its model has hull candidates (bit 0) or force sensors (bit 1): with self_collide, what
+                         // selects the kernel's full form (gs_generic.hip launch_sim_generic)
   // lane-team kernels: envs per wave of a launch, 16 / 8 / 4 (GS_TEAM_ENVS_PER_WAVE at gs_sim_create); 0 = the
   // kernel's own default for the scene (gs_team.hip team_epw)
   int team_epw;
@@ -121,6 +123,9 @@ struct SimBuffers {
 struct GenTopo {
   int nc;
   int cbody[GS_MAXC], cshape[GS_MAXC], clink[GS_MAXC];
+  int cdyn[GS_MAXC];  // hull slot 0..3 of a hull shape's dynamic candidate, -1 for a fixed point candidate
+  int ns;             // collision shapes
+  int npool;          // self-contact pool slots (0: no pair table); the pair table itself is DevModel's pa / pb / pk
 };
 
 struct PdDev {
@@ -215,9 +220,12 @@ hipError_t launch_sim_generic(const DevModel* M, const DevParams& P, const SimBu
                               hipStream_t st);
 hipError_t launch_pd_generic(const DevModel* M, const DevParams& P, const SimBuffers& B, const PdDev& A,
                              hipStream_t st);
-inline size_t generic_ws_floats(int nc, int nd, int fixed_base) {
-  return (size_t)2 * (3 * nc + nd) * ((fixed_base ? 0 : 6) + nd);
+// (rows: 3 per candidate, one per dof limit, 3 per self-contact pool slot; J and W of nv floats each)
+inline size_t generic_ws_floats(int nc, int nd, int fixed_base, int npool) {
+  return (size_t)2 * (3 * nc + nd + 3 * npool) * ((fixed_base ? 0 : 6) + nd);
 }
+hipError_t launch_dbg_pool_generic(const DevModel* M, const DevParams& P, const SimBuffers& B, int mode, float* out,
+                                   int* count, hipStream_t st);
 
 // ---------------------------------------------------------------- host backend (gs_host.hip)
 // The sim_device=cpu pipeline: the same solver on host buffers, envs spread over a thread pool.

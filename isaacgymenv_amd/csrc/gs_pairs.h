@@ -660,6 +660,13 @@ struct ShapeConstsTab {
   GS_HD float hlen(int s) const { return t[kShC * s + 2]; }
 };
 
+// kind of shape s: the compiled topology's constant (T::shkind), or the model's where T has no such table (the
+// runtime-sized kernel, gs_generic.hip)
+template <class T>
+GS_HD auto pair_shape_kind(const DevModel*, int s, int) -> decltype(+T::shkind[s]) { return T::shkind[s]; }
+template <class T>
+GS_HD int pair_shape_kind(const DevModel* __restrict__ M, int s, long) { return M->shkind[s]; }
+
 // One pair (shapes a < b, pair kind) of self_contacts: appends its contacts to the pool (n counts them).
 // REC: a pair record of the wave-assisted lane kernels (gs_physics_impl.h pair_records) -- only x, n and the
 // separation (kRec floats per contact); pool_entry_finish completes the entry as the full form writes it.
@@ -689,7 +696,7 @@ GS_HD __attribute__((always_inline)) inline void self_pair(const DevModel* __res
 #pragma unroll
       for (int k = 0; k < 3; ++k) { pa[0][k] = Wa.c[k]; pb[0][k] = Wb.c[k]; }
     } else if (kind == 1) {
-      const bool a_sph = T::shkind[a] == 0;  // (the compiled topology's kinds: gs_sim_set_model checks them)
+      const bool a_sph = pair_shape_kind<T>(M, a, 0) == 0;  // (compiled kinds: gs_sim_set_model checks them)
       const ShapeW& Wc = a_sph ? Wb : Wa;
       const ShapeW& Ws = a_sph ? Wa : Wb;
       const float hl = sc.hlen(a_sph ? b : a);
