@@ -149,6 +149,8 @@ int rl_ppo_heads_loss_backward(const float *grad_loss, const float *dmu, const f
  * running_mean / running_var [cols] and count (0-d) as the reference does in train mode; then
  * y = clamp((x - float(mean)) / sqrt(float(var) + epsilon), -5, 5).  partials >= ceil(rows / 64) * cols * 2
  * f32 scratch (update only).  Three launches (update) or one.
+ * rows == 1: the batch variance merged is 0, where torch's unbiased var of one row is NaN (which the reference's
+ * merge would keep in running_var for good); the mean and the count are merged as for any batch.
  */
 int rl_rms_normalize(const float *x, int32_t rows, int32_t cols, double *running_mean, double *running_var,
                      double *count, double epsilon, int32_t update, float *partials, float *y, void *stream);

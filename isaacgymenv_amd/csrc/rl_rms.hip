@@ -5,9 +5,12 @@
 // float64 running moments, then y = clamp((x - mean) / sqrt(var + eps), -5, 5) with the float32
 // casts of the running moments.  torch spends ~25 launches on it (a Welford reduction of ~40 us at
 // 16384 x 188, ~15 float64 elementwise ops on [C], the normalisation chain); here:
-//   k_rms_part: workgroup b, lane c = column c: Welford over the workgroup's 64 rows (fp32, loads issued 8 ahead)
-//   k_rms_fin : 64 lanes per column merge the workgroups' (mean, M2) in fp64 (Chan et al.; lane j takes blocks
-//               j, j + 64, ... in order, then a fixed pairwise tree: deterministic), rounds the
+//   k_rms_part: workgroup b, lane c = column c: over the workgroup's 64 rows the sums of d = x - K and d^2 in fp64
+//               (its 64 loads issued at once), K = x[0][c], the batch's first row: one shift for every block of the column,
+//               so the fp32 partials (block mean - K, M2) do not carry the column's offset (a column whose mean is
+//               10^4 standard deviations from 0 keeps its variance; a constant column has M2 == 0 exactly)
+//   k_rms_fin : 64 lanes per column merge the workgroups' (mean - K, M2) in fp64 (Chan et al.; lane j takes blocks
+//               j, j + 64, ... in order, then a fixed pairwise tree: deterministic), adds K back, rounds the
 //               batch mean / var to fp32 as torch's fp32 reductions return them, then updates the running
 //               moments with the reference formula in fp64, same operation order
 //   k_rms_norm: the normalisation (also the eval-mode path, update = 0); bumps the running count
@@ -24,7 +27,7 @@ namespace {
 
 constexpr int kCols = 256;     // columns <= 256
 constexpr int kRowBlock = 64;  // rows per partial
-constexpr int kPre = 8;        // loads issued ahead of the dependent Welford / merge chain
+constexpr int kChains = 8;     // independent fp64 chains of a block's sums
 constexpr int kFinCols = 4;    // finish: columns per workgroup, kFinSub lanes per column
 constexpr int kFinSub = 64;
 
@@ -33,24 +36,33 @@ __global__ __launch_bounds__(kCols) void k_rms_part(const float* __restrict__ x,
     const int c = threadIdx.x;
     if (c >= C) return;
     const int r0 = blockIdx.x * kRowBlock, r1 = min(N, r0 + kRowBlock);
-    float mean = 0.f, m2 = 0.f;
-    int n = 0;
-    for (int r = r0; r < r1; r += kPre) {
-        float v[kPre];
+    // branch-free: all of the block's rows requested at once (one wave per SIMD here, nothing else hides a load);
+    // rows past the block re-read its last row (a valid address; never added)
+    float v[kRowBlock];
 #pragma unroll
-        for (int k = 0; k < kPre; ++k) v[k] = r + k < r1 ? x[(size_t)(r + k) * C + c] : 0.f;
+    for (int k = 0; k < kRowBlock; ++k) v[k] = x[(size_t)min(r0 + k, r1 - 1) * C + c];
+    const double shift = (double)x[c];  // K: the same for every block of the column
+    // kChains independent chains (row r0 + k into chain k % kChains), added pairwise at the end: a fixed order
+    double s[kChains], ss[kChains];
 #pragma unroll
-        for (int k = 0; k < kPre; ++k) {
-            if (r + k < r1) {
-                ++n;
-                const float d = v[k] - mean;
-                mean += d / (float)n;
-                m2 += d * (v[k] - mean);
-            }
+    for (int k = 0; k < kChains; ++k) s[k] = ss[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < kRowBlock; ++k) {
+        const double d = r0 + k < r1 ? (double)v[k] - shift : 0.0;
+        s[k % kChains] += d;
+        ss[k % kChains] += d * d;
+    }
+#pragma unroll
+    for (int st = kChains / 2; st > 0; st >>= 1) {
+#pragma unroll
+        for (int k = 0; k < st; ++k) {
+            s[k] += s[k + st];
+            ss[k] += ss[k + st];
         }
     }
-    part[((size_t)blockIdx.x * C + c) * 2 + 0] = mean;
-    part[((size_t)blockIdx.x * C + c) * 2 + 1] = m2;
+    const double mean = s[0] / (double)(r1 - r0);
+    part[((size_t)blockIdx.x * C + c) * 2 + 0] = (float)mean;                            // block mean - K
+    part[((size_t)blockIdx.x * C + c) * 2 + 1] = (float)fmax(ss[0] - s[0] * mean, 0.0);  // M2 about the block mean
 }
 
 // Chan et al. merge of (na, mean, M2) with (nb, pm, pm2), float64
@@ -65,7 +77,8 @@ __device__ __forceinline__ void merge(double& na, double& mean, double& M2, doub
 // workgroup = kFinCols columns x kFinSub lanes; lane j merges the partials b = j, j + kFinSub, ... in order, then
 // the kFinSub lane results are merged pairwise in a fixed tree (lane j with lane j + s, s = 32, 16, ..., 1):
 // deterministic, and 47 workgroups of short fp64 chains instead of 3 workgroups of 64-long ones (34.5 -> ~2 us)
-__global__ __launch_bounds__(kFinCols * kFinSub) void k_rms_fin(const float* __restrict__ part, int blocks, int N,
+__global__ __launch_bounds__(kFinCols * kFinSub) void k_rms_fin(const float* __restrict__ x,
+                                                                const float* __restrict__ part, int blocks, int N,
                                                                 int C, double* __restrict__ rmean,
                                                                 double* __restrict__ rvar,
                                                                 const double* __restrict__ count) {
@@ -95,7 +108,7 @@ __global__ __launch_bounds__(kFinCols * kFinSub) void k_rms_fin(const float* __r
     if (j != 0 || c >= C) return;
     const double cnt = *count;  // updated by k_rms_norm, after every column's update
     // torch: input.mean / input.var on float32 return float32
-    const double bmean = (double)(float)mean;
+    const double bmean = (double)(float)((double)x[c] + mean);  // k_rms_part's shift added back
     const double bvar = (double)(float)(N > 1 ? M2 / (double)(N - 1) : 0.0);
     const double bc = (double)N;
     // RunningMeanStd._update_mean_var_count_from_moments, same order of operations
@@ -137,8 +150,8 @@ static int rms_normalize(const float* x, int32_t rows, int32_t cols, double* run
     if (update) {
         const int blocks = (rows + kRowBlock - 1) / kRowBlock;
         hipLaunchKernelGGL(k_rms_part, dim3(blocks), dim3(kCols), 0, st, x, (int)rows, (int)cols, partials);
-        hipLaunchKernelGGL(k_rms_fin, dim3((cols + kFinCols - 1) / kFinCols), dim3(kFinCols * kFinSub), 0, st, partials,
-                           blocks, (int)rows, (int)cols, running_mean, running_var, count);
+        hipLaunchKernelGGL(k_rms_fin, dim3((cols + kFinCols - 1) / kFinCols), dim3(kFinCols * kFinSub), 0, st, x,
+                           partials, blocks, (int)rows, (int)cols, running_mean, running_var, count);
     }
     const int64_t n = (int64_t)rows * cols;
     if (half)

@@ -572,3 +572,144 @@ def ppo_heads_minibatch(B, H, A, seed=0):
     h = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.float16)  # noqa: E731
     heads = dict(hidden_a=h(ha), hidden_c=h(hc), w_mu=h(w_mu), b_mu=h(b_mu), w_v=h(w_v), b_v=h(b_v))
     return heads, ppo_minibatch(B, A, seed, mu=h(mu), values=h(v))
+
+
+# ---- the comparison rule of the float64-referenced kernel tests (test_ppo_loss_gpu.py, test_learner_kernels_gpu.py)
+def field_check(tag, seen, fails, what, field, got, r64, r32, zeros=False, err_32=None):
+    """max|kernel - ref64| <= 4 max|ref32 - ref64| + 4 2^-23 max|ref64| for one output field; its figures printed
+    under `tag` and the largest err_kernel / err_f32 and err_kernel / bar kept in seen[field].  err_32: the float32
+    reference's error where the caller has it from more than this one draw (one-number outputs)."""
+    got, r64, r32 = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (got, r64, r32))
+    assert got.shape == r64.shape == r32.shape, (what, field)
+    err_k = float(np.abs(got - r64).max())
+    err_32 = float(np.abs(r32 - r64).max()) if err_32 is None else float(err_32)
+    bar = 4.0 * err_32 + 4.0 * 2.0 ** -23 * float(np.abs(r64).max())
+    r32_ratio = err_k / err_32 if err_32 > 0 else (0.0 if err_k == 0 else float("inf"))
+    print(f"[{tag}] {what} {field}: err_kernel {err_k:.3e} err_f32 {err_32:.3e} ratio {r32_ratio:.3g} "
+          f"bar {bar:.3e} max|ref| {np.abs(r64).max():.3e}")
+    s = seen.setdefault(field, [0.0, 0.0])
+    s[0], s[1] = max(s[0], r32_ratio if np.isfinite(r32_ratio) else 0.0), max(s[1], err_k / bar if bar > 0 else 0.0)
+    if not np.isfinite(got).all() or not err_k <= bar:
+        fails.append(f"{what} {field}: err_kernel {err_k:.3e} > bar {bar:.3e} (err_f32 {err_32:.3e})")
+    if zeros and not np.array_equal(got == 0, r64 == 0):
+        fails.append(f"{what} {field}: zero pattern differs at {np.nonzero((got == 0) != (r64 == 0))[0][:8].tolist()}")
+
+
+# ---- inputs of the learner's bookkeeping kernels (test_learner_oracle.py asserts what is claimed here;
+# ---- test_learner_kernels_gpu.py relies on it)
+# the shapes of tests/test_learner_kernels_gpu.py (rl_rms_normalize rows x cols, rl_policy_kl M x A, rl_act_heads N, H, A)
+RMS_SHAPES = [(1, 3), (2, 1), (63, 5), (64, 8), (65, 256), (4097, 7), (1000, 255)]
+KL_SHAPES = [(1, 1), (255, 12), (257, 12), (1000, 8), (65537, 2)]
+ACT_HEADS_SHAPES = [(1, 1, 1), (15, 3, 1), (17, 5, 12), (33, 128, 12), (16, 130, 64)]
+RMS_KINDS = ("unit", "offset", "small", "constant", "outlier")  # column c is of kind c % 5
+RMS_OFFSET, RMS_SMALL, RMS_CONSTANT = 1.0e4, 1.0e-4, 3.25
+RMS_CLAMP_MARGIN = 1e-3  # |y| within this of 5: the clamp may go either way in f32
+
+
+def rms_kinds(cols):
+    return np.arange(cols) % len(RMS_KINDS)
+
+
+def rms_input(rows, cols, seed=0):
+    """x [rows][cols] f32 with the column kinds mixed (column c: RMS_KINDS[c % 5]): N(0.3, 1); RMS_OFFSET + N(0, 1)
+    (the mean 10^4 standard deviations away); RMS_SMALL N(0, 1); the constant RMS_CONSTANT (M2 == 0); N(0, 1) with
+    every 49th row (r + seed) % 49 == 0 at +-300, the sign alternating (about 7 standard deviations of the column: past the
+    clamp)."""
+    import torch
+    rng = np.random.RandomState(3000 + seed)
+    z = rng.normal(size=(rows, cols))
+    k = rms_kinds(cols)[None, :]
+    r = np.arange(rows)[:, None]
+    far = ((r + seed) % 49 == 0)
+    x = np.where(k == 0, 0.3 + z, np.where(k == 1, RMS_OFFSET + z, np.where(k == 2, RMS_SMALL * z, np.where(
+        k == 3, RMS_CONSTANT, np.where(far, 300.0 * np.where(((r + seed) // 49) % 2 == 0, 1.0, -1.0), z)))))
+    return torch.from_numpy(x.astype(np.float32))
+
+
+def rms_state(cols, count, seed=0):
+    """Float64 running moments a long run over rms_input's columns would hold, at `count` samples."""
+    import torch
+    rng = np.random.RandomState(3500 + seed)
+    k = rms_kinds(cols)
+    mean = np.select([k == 0, k == 1, k == 2, k == 3, k == 4], [0.3, RMS_OFFSET, 0.0, RMS_CONSTANT, 0.0])
+    var = np.select([k == 0, k == 1, k == 2, k == 3, k == 4], [1.0, 1.0, RMS_SMALL ** 2, 1e-12, 1.0 + 9.0e4 / 49])
+    mean = mean + 1e-3 * np.sqrt(var) * rng.normal(size=cols)
+    return torch.from_numpy(mean), torch.from_numpy(var * (1.0 + 1e-3 * rng.normal(size=cols))), float(count)
+
+
+def opt_state(n, step, seed=0):
+    """(p, m, v) f32 [n] of an Adam run at `step`: p = 0.1 N(0, 1) with every 5th element exactly 0 (there the stored
+    parameter carries the step alone); step 0: zero moments; later: m = 1e-3 N(0, 1), v = 1e-6 U(0.5, 2)."""
+    import torch
+    rng = np.random.RandomState(4000 + seed)
+    p = 0.1 * rng.normal(size=n)
+    p[::5] = 0.0
+    m = np.zeros(n) if step == 0 else 1e-3 * rng.normal(size=n)
+    v = np.zeros(n) if step == 0 else 1e-6 * rng.uniform(0.5, 2.0, size=n)
+    return tuple(torch.from_numpy(a.astype(np.float32)) for a in (p, m, v))
+
+
+def opt_grad(n, seed, scale=None):
+    """A gradient [n] f32 = (scale or 1) 10^U(-5, -2) N(0, 1): sqrt(v) runs from far above eps = 1e-8 to 1e3 eps."""
+    import torch
+    rng = np.random.RandomState(4500 + seed)
+    g = rng.normal(size=n) * 10.0 ** rng.uniform(-5.0, -2.0, size=n) * (scale or 1.0)
+    return torch.from_numpy(g.astype(np.float32))
+
+
+KL_SIGMA_MODES = ("log", "row", "full")  # one log-sigma row (stride 0), one sigma row (stride 0), [M][A] sigmas
+KL_KINDS = ("far", "near", "same")
+
+
+def kl_inputs(M, A, kind="far", sigma_mode="log", half=False, seed=0):
+    """dict(mu_new [M][A] fp16 / f32, sigma_new [A] or [M][A] f32 (its log for "log"), mu_old, sigma_old [M][A] f32,
+    sigma_is_log, sigma_row_stride).  far: mu_old = mu_new + 0.1 N(0, 1), sigma_old = sigma_new (1 + 0.05 N(0, 1));
+    near: mu_old = mu_new + 1e-3 N(0, 1) and equal sigmas; same: mu_old == mu_new exactly, equal sigmas."""
+    import torch
+    assert kind in KL_KINDS and sigma_mode in KL_SIGMA_MODES
+    rng = np.random.RandomState(5000 + seed)
+    mu_new = torch.from_numpy(rng.uniform(-1.0, 1.0, (M, A))).to(torch.float16 if half else torch.float32)
+    ls = rng.uniform(-0.7, 0.3, (M, A) if sigma_mode == "full" else (A,))
+    sg_in = torch.from_numpy(ls if sigma_mode == "log" else np.exp(ls)).to(torch.float32)
+    s0 = np.broadcast_to(np.exp(sg_in.double().numpy()) if sigma_mode == "log" else sg_in.double().numpy(), (M, A))
+    dmu = dict(far=0.1, near=1e-3, same=0.0)[kind] * rng.normal(size=(M, A))
+    mu_old = torch.from_numpy(mu_new.double().numpy() + dmu).to(torch.float32)
+    s1 = s0 * (1.0 + 0.05 * rng.normal(size=(M, A))) if kind == "far" else s0
+    return dict(mu_new=mu_new, sigma_new=sg_in.contiguous(), mu_old=mu_old,
+                sigma_old=torch.from_numpy(np.array(s1)).to(torch.float32),
+                sigma_is_log=int(sigma_mode == "log"), sigma_row_stride=A if sigma_mode == "full" else 0)
+
+
+def kl_scheduler_cases(kl):
+    """(threshold, lr, expected lr) around a float64 KL: every threshold puts 2 thr and thr / 2 at a factor of 2
+    from the KL, and both clamps (1e-6, 1e-2) are reached."""
+    return [(kl / 4, 3e-4, 3e-4 / 1.5), (kl * 4, 3e-4, 3e-4 * 1.5), (kl, 3e-4, 3e-4), (kl / 4, 1.2e-6, 1e-6),
+            (kl / 4, 1e-6, 1e-6), (kl * 4, 8e-3, 1e-2), (kl * 4, 1e-2, 1e-2)]
+
+
+def act_heads_inputs(N, H, A, seed=0, sharp=False):
+    """Real-valued act-forward head inputs: hidden [N][2H + 4] f32 (actor columns [0, H), critic [H, 2H), the pad
+    NaN: never to be read), w_mu [A][H], b_mu [A], w_v [H], b_v [1], noise [N][A], logstd [A], and the value
+    RunningMeanStd's float64 moments vmean, vvar [1].  The raw value has a standard deviation of about 4 (both sides
+    of +-5).  sharp: logstd = -5 and b_mu = +-1e3, so |mu| ~ 1e3 against sigma = 0.0067."""
+    import torch
+    rng = np.random.RandomState(6000 + seed)
+    hid = np.full((N, 2 * H + 4), np.nan)
+    hid[:, :2 * H] = rng.normal(size=(N, 2 * H))
+    w_mu = rng.normal(size=(A, H)) / np.sqrt(H)
+    b_mu = np.where(np.arange(A) % 2 == 0, 1.0, -1.0) * 1.0e3 if sharp else 0.1 * rng.normal(size=A)
+    w_v = 4.0 * rng.normal(size=H) / np.sqrt(H)
+    b_v = rng.normal(size=1)
+    logstd = np.full(A, -5.0) if sharp else rng.uniform(-1.0, 0.5, A)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(torch.float32)  # noqa: E731
+    return dict(hidden=t(hid), w_mu=t(w_mu), b_mu=t(b_mu), w_v=t(w_v), b_v=t(b_v), noise=t(rng.normal(size=(N, A))),
+                logstd=t(logstd), vmean=torch.tensor([0.731], dtype=torch.float64),
+                vvar=torch.tensor([2.37], dtype=torch.float64))
+
+
+def colsum_inputs(rows, cols, half, seed=0):
+    """(g [rows][cols] fp16 / f32 = N(0, 1), grad [cols] f32 = N(0, 1): a nonzero gradient to accumulate onto)."""
+    import torch
+    rng = np.random.RandomState(7000 + seed)
+    g = torch.from_numpy(rng.normal(size=(rows, cols))).to(torch.float16 if half else torch.float32)
+    return g, torch.from_numpy(rng.normal(size=cols)).to(torch.float32)

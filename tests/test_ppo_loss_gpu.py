@@ -84,20 +84,9 @@ def _bits(t):
 
 
 def _field(fails, what, field, got, r64, r32, zeros=False):
-    """The rule of the module docstring for one field; its figures printed and kept for the report."""
-    got, r64, r32 = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (got, r64, r32))
-    assert got.shape == r64.shape == r32.shape, (what, field)
-    err_k, err_32 = float(np.abs(got - r64).max()), float(np.abs(r32 - r64).max())
-    bar = 4.0 * err_32 + 4.0 * 2.0 ** -23 * float(np.abs(r64).max())
-    r32_ratio = err_k / err_32 if err_32 > 0 else (0.0 if err_k == 0 else float("inf"))
-    print(f"[ppo-loss] {what} {field}: err_kernel {err_k:.3e} err_f32 {err_32:.3e} ratio {r32_ratio:.3g} "
-          f"bar {bar:.3e} max|ref| {np.abs(r64).max():.3e}")
-    s = SEEN.setdefault(field, [0.0, 0.0])
-    s[0], s[1] = max(s[0], r32_ratio if np.isfinite(r32_ratio) else 0.0), max(s[1], err_k / bar if bar > 0 else 0.0)
-    if not np.isfinite(got).all() or not err_k <= bar:
-        fails.append(f"{what} {field}: err_kernel {err_k:.3e} > bar {bar:.3e} (err_f32 {err_32:.3e})")
-    if zeros and not np.array_equal(got == 0, r64 == 0):
-        fails.append(f"{what} {field}: zero pattern differs at {np.nonzero((got == 0) != (r64 == 0))[0][:8].tolist()}")
+    """The rule of the module docstring for one field (tests/helpers.py field_check); its figures printed and kept
+    for the report."""
+    H.field_check("ppo-loss", SEEN, fails, what, field, got, r64, r32, zeros=zeros)
 
 
 GRADS, MEANS = "gradients", "means"  # the two halves of the outputs, a test each
