@@ -263,6 +263,13 @@ int rl_opt_step_h(float *param, void *param_half, const float *grad, float *exp_
  *   layout bpart = wpart + N*K, pstride = N*K + N: one rl_splitk_accum finishes a weight and its bias when their
  *   gradients are adjacent).  wpart 16-byte aligned.  Finish with rl_splitk_accum (fixed order).  M % 128 == 0,
  *   M % (64 splits) == 0.
+ * The roundings (oracle/linear_oracle.py restates them; tests/test_linear_kernels_gpu.py holds the kernels to them):
+ *   forward: the products and their sum in f32, the bias (widened to f32) added in f32 before ELU, ELU in f32, and y
+ *   rounded ONCE to fp16.  Backward: dZ is the f32 product f32(dy) * f32(y > 0 ? 1 : y + 1) rounded ONCE to fp16, and
+ *   dx, wpart and bpart all use that rounded dZ (f32 products and sums); dx is rounded once to fp16.  bpart[s][n] is
+ *   the f32 sum of sixteen row-group sums added in ascending group order from 0, group g being the block's rows
+ *   r = g mod 16 added in ascending order from 0.
+ * Both entry points (and their grouped forms) refuse ldx < K.
  */
 int rl_linear_fwd(const void *x, int32_t M, int32_t K, int32_t ldx, const void *w, int32_t N, const void *bias,
                   int32_t act, void *y, void *stream);

@@ -632,6 +632,7 @@ extern "C" int rl_linear_fwd_g(const void* x, int32_t M, int32_t K, int32_t ldx,
   if (G < 1 || G > 65535 || ldy < N || ldy % 4) return rl_set_error("rl_linear_fwd: bad groups or output row stride");
   if (M % 64 || N % 128 || ldx % 4 || K % 4 || !aligned8(x) || !aligned8(w) || !aligned8(y))
     return rl_set_error("rl_linear_fwd: M % 64, N % 128, K % 4 and 8-byte aligned rows required");
+  if (ldx < K) return rl_set_error("rl_linear_fwd: the input row stride ldx is below K");
   const int64_t gx = grp ? grp->x_gstride : 0, gw = grp ? grp->w_gstride : 0, gb = grp ? grp->b_gstride : 0,
                 gy = grp ? grp->y_gstride : 0;
   if (G > 1 && ((gx | gw | gb | gy) % 4 != 0)) return rl_set_error("rl_linear_fwd: group strides must be % 4");
@@ -709,6 +710,7 @@ extern "C" int rl_linear_bwd_g(const void* dy, const void* y, int32_t M, int32_t
     return rl_set_error("rl_linear_bwd: bad groups or row strides");
   if (M % 128 || N % 128 || K % 4 || ldx % 4 || !aligned8(dy) || !aligned8(y) || !aligned8(x))
     return rl_set_error("rl_linear_bwd: M % 128, N % 128, K % 4 and 8-byte aligned rows required");
+  if (ldx < K) return rl_set_error("rl_linear_bwd: the input row stride ldx is below K");
   if (splits <= 0 || M % (splits * kTnStep) != 0 || (int64_t)splits * G > 65535)
     return rl_set_error("rl_linear_bwd: M must split into row blocks of multiples of 64");
   // (the bias partials come out of the weight-gradient kernel's pass: bpart alone would be left unwritten)
@@ -720,9 +722,16 @@ extern "C" int rl_linear_bwd_g(const void* dy, const void* y, int32_t M, int32_t
   const auto* DY = static_cast<const _Float16*>(dy);
   const auto* Yv = static_cast<const _Float16*>(y);
   const auto* X = static_cast<const _Float16*>(x);
+  // every refusal comes before the first launch: a refused call writes nothing
+  if (dx && (!w || !aligned8(w) || !aligned8(dx) || K % 128))
+    return rl_set_error("rl_linear_bwd: dX needs W, 8-byte aligned rows and K % 128");
+  // pstride 0: wpart [splits][N][K], bpart [splits][N]; else both advance pstride floats per block (the merged
+  // layout: each block's bias partials right behind its weight partials, pstride = N*K + N; grouped: the groups'
+  // weight partials then their bias partials within a block, pstride = G (N*K + N))
+  const int64_t ws = pstride ? pstride : (int64_t)N * K, bs = pstride ? pstride : (int64_t)N;
+  if (wpart && ((reinterpret_cast<uintptr_t>(wpart) & 15) || ws % 4 || ws < (int64_t)N * K))
+    return rl_set_error("rl_linear_bwd: weight partials need 16-byte alignment and a block stride >= N*K, % 4");
   if (dx) {
-    if (!w || !aligned8(w) || !aligned8(dx) || K % 128)
-      return rl_set_error("rl_linear_bwd: dX needs W, 8-byte aligned rows and K % 128");
     const auto* Wp = static_cast<const _Float16*>(w);
     auto* DX = static_cast<_Float16*>(dx);
     static const int nn_wg = getenv("RL_NN_WG") ? atoi(getenv("RL_NN_WG")) : 256;  // (A/B switch)
@@ -735,12 +744,6 @@ extern "C" int rl_linear_bwd_g(const void* dy, const void* y, int32_t M, int32_t
     if (int rc = launch_fail("rl_linear_bwd (dX)")) return rc;
   }
   if (wpart) {
-    // pstride 0: wpart [splits][N][K], bpart [splits][N]; else both advance pstride floats per block (the merged
-    // layout: each block's bias partials right behind its weight partials, pstride = N*K + N; grouped: the groups'
-    // weight partials then their bias partials within a block, pstride = G (N*K + N))
-    const int64_t ws = pstride ? pstride : (int64_t)N * K, bs = pstride ? pstride : (int64_t)N;
-    if ((reinterpret_cast<uintptr_t>(wpart) & 15) || ws % 4 || ws < (int64_t)N * K)
-      return rl_set_error("rl_linear_bwd: weight partials need 16-byte alignment and a block stride >= N*K, % 4");
     hipLaunchKernelGGL(k_gemm_tn, dim3(N / kTN, (K + kTN - 1) / kTN, splits * G), dim3(kThreads), 0, st, DY, Yv, N,
                        ldy, X, ldx, K, M / splits, wpart, bpart, ws, bs, splits, gy, gx, gp, gbp);
     return launch_fail("rl_linear_bwd (dW)");

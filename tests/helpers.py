@@ -595,6 +595,24 @@ def field_check(tag, seen, fails, what, field, got, r64, r32, zeros=False, err_3
         fails.append(f"{what} {field}: zero pattern differs at {np.nonzero((got == 0) != (r64 == 0))[0][:8].tolist()}")
 
 
+def np64(t):
+    """float64 numpy of a tensor (any device / dtype) or of a list of Python floats."""
+    import torch
+    return t.detach().double().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float64)
+
+
+def bits(t):
+    """The tensor's bit patterns as integers, on the CPU."""
+    import torch
+    t = t.detach().cpu().contiguous()
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def same_bits(a, b):
+    import torch
+    return torch.equal(bits(a), bits(b))
+
+
 # ---- inputs of the learner's bookkeeping kernels (test_learner_oracle.py asserts what is claimed here;
 # ---- test_learner_kernels_gpu.py relies on it)
 # the shapes of tests/test_learner_kernels_gpu.py (rl_rms_normalize rows x cols, rl_policy_kl M x A, rl_act_heads N, H, A)
@@ -713,3 +731,147 @@ def colsum_inputs(rows, cols, half, seed=0):
     rng = np.random.RandomState(7000 + seed)
     g = torch.from_numpy(rng.normal(size=(rows, cols))).to(torch.float16 if half else torch.float32)
     return g, torch.from_numpy(rng.normal(size=cols)).to(torch.float32)
+
+
+# ---- the matrix-core Linear + ELU kernels (test_linear_oracle.py asserts what is claimed here;
+# ---- test_linear_kernels_gpu.py relies on it)
+def elementwise_bound(ref64, S, terms, out_half):
+    """Per element: h + (terms + 2) 2^-24 S + 4 2^-24 |ref64|.  (terms + 2) 2^-24 S: the forward error bound of an f32
+    dot product of `terms` products summed in any order (S = the same sum on absolute values), two more roundings for
+    the bias and the epilogue; 4 f32 ulp for expm1f; h: half the fp16 spacing at fp16(ref64) when the output is
+    rounded to fp16 (0 for f32 outputs; where fp16(ref64) is infinite the bound is infinite: the caller judges
+    overflow by its pattern)."""
+    ref64, S = np.asarray(ref64, dtype=np.float64), np.asarray(S, dtype=np.float64)
+    u = 2.0 ** -24
+    bound = (terms + 2) * u * S + 4.0 * u * np.abs(ref64)
+    if out_half:
+        with np.errstate(over="ignore", invalid="ignore"):
+            r16 = ref64.astype(np.float16)
+            fin = np.isfinite(r16)
+            # the spacing of the binade |fp16(ref64)| lies in (at a power of two: the wider side, which its rounding
+            # interval reaches half of), 2^-24 in the subnormals
+            _, e = np.frexp(np.where(fin, np.abs(r16), 0).astype(np.float64))
+            h = 0.5 * np.maximum(np.ldexp(1.0, e - 11), 2.0 ** -24)
+        bound = bound + np.where(fin, h, np.inf)
+    return bound
+
+
+def elementwise_check(tag, seen, fails, what, field, got, ref64, S, terms, out_half, act=False):
+    """Every element of one output field: |got - ref64| <= elementwise_bound (ref64 unrounded).  act: the field went
+    through ELU, which is 1-Lipschitz, so the dot product's bound holds for it unchanged (it only labels the
+    figures).  Prints the largest err / bound under `tag`, keeps it in seen[field], and returns (that ratio, the
+    fraction of elements beyond the bound)."""
+    got, ref64 = (np.asarray(x, dtype=np.float64).reshape(-1) for x in (got, ref64))
+    bound = elementwise_bound(ref64, np.asarray(S, dtype=np.float64).reshape(-1), terms, out_half)
+    assert got.shape == ref64.shape == bound.shape, (what, field)
+    err = np.abs(got - ref64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(bound > 0, err / bound, np.where(err == 0, 0.0, np.inf))
+    ratio = np.where(np.isfinite(got), ratio, np.inf)
+    worst, beyond = float(ratio.max()), float((ratio > 1.0).mean())
+    print(f"[{tag}] {what} {field}{' (ELU)' if act else ''}: elementwise err / bound <= {worst:.3g} over {got.size} "
+          f"elements, {beyond:.3%} beyond, terms {terms}")
+    seen[field] = max(seen.get(field, 0.0), worst if np.isfinite(worst) else 0.0)
+    if not worst <= 1.0:
+        at = int(np.argmax(ratio))
+        fails.append(f"{what} {field}: elementwise err / bound {worst:.3g} at flat index {at} (got {got[at]!r}, ref "
+                     f"{ref64[at]!r}, bound {bound[at]:.3e}); {beyond:.3%} of the elements beyond the bound")
+    return worst, beyond
+
+
+def linear_inputs(M, K, N, seed=0, G=1):
+    """x [G][M][K] ~ 1.5 N(0, 1), w [G][N][K] ~ N(0, 0.08 sqrt(188 / K)), bias [G][N] ~ 0.1 N(0, 1): drawn in f32
+    (x32, w32, b32: what the f32 kernel gets) and rounded to fp16 (x, w, b).  The pre-activations have a standard
+    deviation of about 1.65 at every K and straddle 0."""
+    import torch
+    rng = np.random.RandomState(9000 + seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    x32 = t(1.5 * rng.normal(size=(G, M, K)))
+    w32 = t(0.08 * np.sqrt(188.0 / K) * rng.normal(size=(G, N, K)))
+    b32 = t(0.1 * rng.normal(size=(G, N)))
+    return dict(x32=x32, w32=w32, b32=b32, x=x32.to(torch.float16), w=w32.to(torch.float16), b=b32.to(torch.float16))
+
+
+LIN_SPECIAL_Y = (("zero", 0.0), ("negzero", -0.0), ("minus_one", -1.0), ("tiny_neg", -2.0 ** -24), ("max", 65504.0))
+
+
+def linear_special_elements(M, N):
+    """{name: (value, rows, cols)}: the elements of y that linear_bwd_inputs overwrites.  Special i takes the whole
+    of row 1 + i and the two elements (16 + 3 i, (5 + 37 i) % N) and (M - 1 - i, (N - 1 - 11 i) % N)."""
+    out = {}
+    for i, (name, v) in enumerate(LIN_SPECIAL_Y):
+        rows = np.concatenate([np.full(N, 1 + i), [16 + 3 * i, M - 1 - i]])
+        cols = np.concatenate([np.arange(N), [(5 + 37 * i) % N, (N - 1 - 11 * i) % N]])
+        out[name] = (v, rows, cols)
+    return out
+
+
+def linear_single_term_column(i, N):
+    """The one column where dy of special row 1 + i is nonzero (every special but minus_one)."""
+    return (7 + 13 * i) % N
+
+
+def linear_bwd_inputs(M, K, N, seed=0, G=1):
+    """linear_inputs plus y [G][M][N] = the float64 reference's fp16 ELU output on them (a real layer output) with
+    the elements of linear_special_elements overwritten, and dy [G][M][N] ~ N(0, 1) in fp16.  In the special rows
+    of 0, -0, the largest fp16 below 0 and 65504, dy is zero except at linear_single_term_column: dZ has one nonzero
+    term there, so that row of dx is one exact product rounded once.  The row of -1 keeps its random dy: its dZ and
+    its row of dx are exactly 0."""
+    import torch
+    from oracle import linear_oracle as LO
+    d = linear_inputs(M, K, N, seed, G)
+    rng = np.random.RandomState(9500 + seed)
+    y = torch.stack([LO.linear_fwd(d["x"][g], d["w"][g], d["b"][g], True)[1] for g in range(G)])
+    dy = torch.from_numpy(rng.normal(size=(G, M, N))).to(torch.float16)
+    for i, (name, (v, rows, cols)) in enumerate(linear_special_elements(M, N).items()):
+        y[:, rows, cols] = torch.tensor(v, dtype=torch.float16)
+        if name != "minus_one":
+            c = linear_single_term_column(i, N)
+            keep = dy[:, 1 + i, c].clone()
+            dy[:, 1 + i, :] = 0
+            dy[:, 1 + i, c] = torch.where(keep == 0, torch.ones_like(keep), keep)
+    d.update(y=y, dy=dy)
+    return d
+
+
+def _lin(M, N, K, G=1, **kw):
+    return dict(M=M, N=N, K=K, G=G, **kw)
+
+
+# rl_linear_fwd(_g): y_off = element offset of y in its 16-byte aligned buffer; ldx / ldy 0 = dense; gaps: the
+# grouped layout with every stride distinct (see test_linear_kernels_gpu._fwd_layout)
+LIN_FWD_CASES = (
+    [_lin(64, 128, K) for K in (4, 36, 60, 64, 68, 128, 132, 188, 196)]            # stage edges of kNtStep = 64
+    + [_lin(128, 384, 68), _lin(192, 128, 36, ldx=44)]                               # N not a power of two; ldx > K
+    + [_lin(M, 128, 36) for M in (320, 576, 832)] + [_lin(320, 384, 36)]             # 5, 9, 13, 15 tiles (1, 3 above)
+    + [_lin(4096, 1024, 36), _lin(1024, 512, 36, G=8), _lin(3968, 1024, 36)]         # 128-row form, grouped, just under
+    + [_lin(128, 128, 68, y_off=4), _lin(128, 128, 68, ldy=132),                     # direct-store arm
+       _lin(128, 128, 68, G=2, ldy=264, y_gstride=132),                              # ... in group 1 only
+       _lin(128, 128, 68, G=3, gaps=True)])
+LIN_F32_CASES = (
+    [_lin(64, 64, K, kstep=ks) for K in (4, 28, 32, 36, 60, 64, 68, 188) for ks in ("32", "64")]
+    + [_lin(512, 4096, 36), _lin(2112, 1024, 36)]                                    # 512 / 528 tiles: default stage 64 / 32
+    + [_lin(128, 64, 36, G=3, ldy=200, y_gstride=68)]
+    + [_lin(192, 64, 36), _lin(576, 64, 36), _lin(320, 192, 36)])                    # 3, 9, 15 tiles (1 above)
+LIN_DX_CASES = (
+    [_lin(128, N, 128, lddx=ld) for N in (128, 384) for ld in (128, 132, 136)]
+    + [_lin(4096, 128, 1024), _lin(3968, 128, 1024), _lin(128, 128, 128, G=3, gaps=True)])
+LIN_DW_SPLITS = ((128, 2), (128, 1), (384, 2), (384, 1), (1024, 16))  # rows_per_split 64, 128, 192, 384, 64
+LIN_DW_N = (128, 384)
+LIN_DW_K = (4, 124, 128, 132, 188)
+SPLITK_PARTS = (1, 15, 16, 17, 33)
+SPLITK_N = (4, 260, 1539)
+TRANSPOSE_SHAPES = ((1, 4), (33, 36), (128, 188))
+
+
+def linear_fwd_tiles(c, f32=False):
+    """Workgroups of a forward case, as the entry points choose their tiles (csrc/rl_linear.hip)."""
+    if f32:
+        return (c["M"] // 64) * (c["N"] // 64) * c["G"]
+    big = (c["M"] // 128) * (c["N"] // 128) * c["G"]
+    return big if big >= 256 and c["M"] % 128 == 0 else (c["M"] // 64) * (c["N"] // 128) * c["G"]
+
+
+def linear_dx_tiles(c):
+    big = (c["M"] // 128) * (c["K"] // 128) * c["G"]
+    return big if big >= 256 else (c["M"] // 64) * (c["K"] // 128) * c["G"]

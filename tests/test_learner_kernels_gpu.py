@@ -107,18 +107,7 @@ def _untouched(bufs, what):
         assert bool(torch.isnan(buf).all()), f"{what}: wrote {k}"
 
 
-def _np(t):
-    """float64 numpy of a tensor (any device / dtype) or of a list of Python floats."""
-    return t.detach().double().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float64)
-
-
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
+_np, _bits, _same_bits = H.np64, H.bits, H.same_bits  # shared with the other float64-referenced kernel modules
 
 
 def _field(fails, what, field, got, r64, r32, err_32=None):
