@@ -1047,6 +1047,39 @@ __device__ __forceinline__ float terrain_candidate(const DevParams& P, const flo
   return dist;
 }
 
+// Body k of the lane's chain from its parent's pose (Rp, Xp): R = Rp jR Rq(q), X = Xp + Rp jt for a revolute joint,
+// R = Rp jR, X = Xp + Rp jt + q aw for a prismatic one; aw: the joint axis in world axes.  (R, X may be Rp, Xp.)
+template <class T>
+__device__ __forceinline__ void joint_pose(const float* cm, int k, float qj, const float* Rp, const float* Xp, float* R,
+                                           float* X, float* aw) {
+  constexpr int LN = T::T_LANES;
+  const float* bp = cm + (k * CM<T>::BODY) * LN;
+  float jR[9], jt[3], ax[3];
+#pragma unroll
+  for (int f = 0; f < 9; ++f) jR[f] = bp[f * LN];
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { jt[f] = bp[(9 + f) * LN]; ax[f] = bp[(12 + f) * LN]; }
+  float RJ[9], t[3];
+  mat3mul(Rp, jR, RJ);
+  mat3vec(Rp, jt, t);
+  X[0] = Xp[0] + t[0]; X[1] = Xp[1] + t[1]; X[2] = Xp[2] + t[2];
+  mat3vec(RJ, ax, aw);
+  if (T::jkind[1 + k] == 1) {
+    float sn, cs;
+    sincosf(qj, &sn, &cs);
+    const float Cc = 1.f - cs;
+    float Rq[9];
+    Rq[0] = cs + ax[0] * ax[0] * Cc;         Rq[1] = ax[0] * ax[1] * Cc - ax[2] * sn; Rq[2] = ax[0] * ax[2] * Cc + ax[1] * sn;
+    Rq[3] = ax[1] * ax[0] * Cc + ax[2] * sn; Rq[4] = cs + ax[1] * ax[1] * Cc;         Rq[5] = ax[1] * ax[2] * Cc - ax[0] * sn;
+    Rq[6] = ax[2] * ax[0] * Cc - ax[1] * sn; Rq[7] = ax[2] * ax[1] * Cc + ax[0] * sn; Rq[8] = cs + ax[2] * ax[2] * Cc;
+    mat3mul(RJ, Rq, R);
+  } else {
+#pragma unroll
+    for (int f = 0; f < 9; ++f) R[f] = RJ[f];
+    X[0] += aw[0] * qj; X[1] += aw[1] * qj; X[2] += aw[2] * qj;
+  }
+}
+
 template <class T, bool TERR, bool TGS, int EPW, bool ROWL, bool RES>
 __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, const float* __restrict__ mdl,
                                              const DevParams& P, TeamState<T>& s, const float* tau,
@@ -1094,7 +1127,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
 
   // ================= TERR: the mesh queries first, while little else is live (run inside the forward pass, where
   // the chain's spatial quantities are live, the query code spilled ~1 KB of registers per lane to scratch).  The
-  // chain's body poses are walked here by the forward pass's own statements; results: distance, normal, friction.
+  // chain's body poses are walked here by the forward pass's own joint_pose; results: distance, normal, friction.
   // (held in a type that is empty for plane scenes: dead arrays there cost the plane kernel 0.5 KB of scratch)
   struct TerrQ {
     float d[CC], n[CC][3], m[CC];                                        // chain candidates
@@ -1114,32 +1147,8 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
     for (int f = 0; f < 9; ++f) Rk[f] = R0[f];
 #pragma unroll
     for (int k = 0; k < CL; ++k) {
-      const float* bp = cm + (k * C::BODY) * LN;
-      float jR[9], jt[3], ax[3];
-#pragma unroll
-      for (int f = 0; f < 9; ++f) jR[f] = bp[f * LN];
-#pragma unroll
-      for (int f = 0; f < 3; ++f) { jt[f] = bp[(9 + f) * LN]; ax[f] = bp[(12 + f) * LN]; }
-      float RJ[9], t[3], aw[3];
-      mat3mul(Rk, jR, RJ);
-      mat3vec(Rk, jt, t);
-      Xk[0] += t[0]; Xk[1] += t[1]; Xk[2] += t[2];
-      mat3vec(RJ, ax, aw);
-      const float qj = s.q[k];
-      if (T::jkind[1 + k] == 1) {
-        float sn, cs;
-        sincosf(qj, &sn, &cs);
-        const float Cc = 1.f - cs;
-        float Rq[9];
-        Rq[0] = cs + ax[0] * ax[0] * Cc;         Rq[1] = ax[0] * ax[1] * Cc - ax[2] * sn; Rq[2] = ax[0] * ax[2] * Cc + ax[1] * sn;
-        Rq[3] = ax[1] * ax[0] * Cc + ax[2] * sn; Rq[4] = cs + ax[1] * ax[1] * Cc;         Rq[5] = ax[1] * ax[2] * Cc - ax[0] * sn;
-        Rq[6] = ax[2] * ax[0] * Cc - ax[1] * sn; Rq[7] = ax[2] * ax[1] * Cc + ax[0] * sn; Rq[8] = cs + ax[2] * ax[2] * Cc;
-        mat3mul(RJ, Rq, Rk);
-      } else {
-#pragma unroll
-        for (int f = 0; f < 9; ++f) Rk[f] = RJ[f];
-        Xk[0] += aw[0] * qj; Xk[1] += aw[1] * qj; Xk[2] += aw[2] * qj;
-      }
+      float aw[3];
+      joint_pose<T>(cm, k, s.q[k], Rk, Xk, Rk, Xk, aw);
 #pragma unroll
       for (int j = 0; j < CC; ++j) {
         if (T::T_ccb[j] == k) {
@@ -1263,33 +1272,12 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   for (int k = 0; k < CL; ++k) {
     const float* Rp = k == 0 ? R0 : R[k - 1];
     const float* Xp = k == 0 ? X0 : X[k - 1];
-    const float* bp = cm + (k * C::BODY) * LN;
-    float jR[9], jt[3], ax[3];
-#pragma unroll
-    for (int f = 0; f < 9; ++f) jR[f] = bp[f * LN];
-#pragma unroll
-    for (int f = 0; f < 3; ++f) { jt[f] = bp[(9 + f) * LN]; ax[f] = bp[(12 + f) * LN]; }
-    float RJ[9], t[3], aw[3];
-    mat3mul(Rp, jR, RJ);
-    mat3vec(Rp, jt, t);
-    X[k][0] = Xp[0] + t[0]; X[k][1] = Xp[1] + t[1]; X[k][2] = Xp[2] + t[2];
-    mat3vec(RJ, ax, aw);
-    const float qj = s.q[k];
+    float aw[3];
+    joint_pose<T>(cm, k, s.q[k], Rp, Xp, R[k], X[k], aw);
     if (T::jkind[1 + k] == 1) {
-      float sn, cs;
-      sincosf(qj, &sn, &cs);
-      const float Cc = 1.f - cs;
-      float Rq[9];
-      Rq[0] = cs + ax[0] * ax[0] * Cc;         Rq[1] = ax[0] * ax[1] * Cc - ax[2] * sn; Rq[2] = ax[0] * ax[2] * Cc + ax[1] * sn;
-      Rq[3] = ax[1] * ax[0] * Cc + ax[2] * sn; Rq[4] = cs + ax[1] * ax[1] * Cc;         Rq[5] = ax[1] * ax[2] * Cc - ax[0] * sn;
-      Rq[6] = ax[2] * ax[0] * Cc - ax[1] * sn; Rq[7] = ax[2] * ax[1] * Cc + ax[0] * sn; Rq[8] = cs + ax[2] * ax[2] * Cc;
-      mat3mul(RJ, Rq, R[k]);
       S[k][0] = aw[0]; S[k][1] = aw[1]; S[k][2] = aw[2];
       cross3(X[k], aw, &S[k][3]);
     } else {
-#pragma unroll
-      for (int f = 0; f < 9; ++f) R[k][f] = RJ[f];
-      X[k][0] += aw[0] * qj; X[k][1] += aw[1] * qj; X[k][2] += aw[2] * qj;
       S[k][0] = S[k][1] = S[k][2] = 0.f;
       S[k][3] = aw[0]; S[k][4] = aw[1]; S[k][5] = aw[2];
     }
