@@ -351,19 +351,38 @@ __device__ __forceinline__ void stage_chain_model(const DevModel* __restrict__ M
 
 // Team-uniform shape constants of the self-collision passes, staged once per launch: per shape
 // (ShapeConstsTab) bounding radius, margin, capsule half length, 256 body + link; then per root shape the core segment in
-// the root frame (ends l0, l1), radius and half length (broadphase)
+// the root frame (ends l0, l1), radius and half length (broadphase).  After them (every topology, self-collision or
+// not) the launch constants of the replicated root, the DevModel words a substep and the root output read: the root
+// body's mass, com (3) and inertia (6), the root candidates' cpoint (3) and cradius, root_com (3) -- so that past
+// the staging barrier a substep loads nothing of the model from device memory (launch constants)
 template <class T>
 struct ShapeTab {
   static constexpr int RS = T::HAS_TEAM ? T::T_RS : 0;
+  static constexpr int RC = T::HAS_TEAM ? T::T_RC : 0;
   static constexpr int ROOT = kShC * T::NS;
   static constexpr int POSE = ROOT + 8 * RS;  // per shape: local R (9), t (3), bounding-sphere centre (3)
-  static constexpr int SIZE = T::NPK > 0 ? POSE + 15 * T::NS : 1;
+  static constexpr int SHAPES = T::NPK > 0 ? POSE + 15 * T::NS : 0;
+  static constexpr int BODY0 = SHAPES;       // mass, com (3), inertia (6)
+  static constexpr int RCAND = BODY0 + 10;   // per root candidate: cpoint (3), cradius
+  static constexpr int RCOM = RCAND + 4 * RC;
+  static constexpr int SIZE = RCOM + 3;
 };
 template <class T>
 __device__ __forceinline__ void stage_shape_consts(const DevModel* __restrict__ M, float* sct) {
+  using S = ShapeTab<T>;
+  // (one load per field, as the shape constants below: selecting each word's place in DevModel first and taking one
+  // load measured no faster, profiles/r12_launch_constants_ab.txt)
+  for (int i = S::SHAPES + (int)threadIdx.x; i < S::SIZE; i += blockDim.x) {
+    const int f = i - S::BODY0;
+    float v;
+    if (i < S::RCAND) v = f == 0 ? M->mass[0] : (f < 4 ? M->com[0][f - 1] : M->inertia[0][f - 4]);
+    else if (i < S::RCOM) v = ((i - S::RCAND) & 3) < 3 ? M->cpoint[(i - S::RCAND) >> 2][(i - S::RCAND) & 3]
+                                                       : M->cradius[(i - S::RCAND) >> 2];
+    else v = M->root_com[i - S::RCOM];
+    sct[i] = v;
+  }
   if constexpr (T::NPK > 0) {
-    using S = ShapeTab<T>;
-    for (int i = threadIdx.x; i < S::SIZE; i += blockDim.x) {
+    for (int i = threadIdx.x; i < S::SHAPES; i += blockDim.x) {
       float v = 0.f;
       if (i < S::ROOT) {
         const int sh = i / kShC, f = i - kShC * sh;
@@ -1081,7 +1100,7 @@ __device__ __forceinline__ void joint_pose(const float* cm, int k, float qj, con
 }
 
 template <class T, bool TERR, bool TGS, int EPW, bool ROWL, bool RES>
-__device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, const float* __restrict__ mdl,
+__device__ __forceinline__ void substep_team(const DevModel* __restrict__ M, const float* __restrict__ mdl,
                                              const DevParams& P, TeamState<T>& s, const float* tau,
                                              const float* __restrict__ mu_t, int N, int e, int lc,
                                              float* __restrict__ rows_own, const float* __restrict__ rows_team,
@@ -1096,9 +1115,9 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   [[maybe_unused]] const int row_own = ROWL ? team_row_of_copy() : 0;
   using C = CM<T>;
   using RS = RowSlots<T>;
-  uintptr_t mp = reinterpret_cast<uintptr_t>(Min);
-  asm volatile("" : "+s"(mp));
-  const DevModel* __restrict__ M = reinterpret_cast<const DevModel*>(mp);
+  // the root's launch constants (ShapeTab; M itself goes to the rare narrowphase only)
+  const float* rb0 = sct + ShapeTab<T>::BODY0;
+  [[maybe_unused]] const float* rcand = sct + ShapeTab<T>::RCAND;
   const float* cm = mdl + lc;  // this lane's chain constants: cm[p * LN]
   const float h = P.h;
 
@@ -1114,7 +1133,7 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
   float nub[6] = {s.w[0], s.w[1], s.w[2], s.vo[0], s.vo[1], s.vo[2]};
   const float A0[6] = {0.f, 0.f, 0.f, -P.g[0], -P.g[1], -P.g[2]};
   SpI I0;
-  body_inertia(R0, X0, M->mass[0], M->com[0], M->inertia[0], I0);
+  body_inertia(R0, X0, rb0[0], rb0 + 1, rb0 + 4, I0);
   float F0[6];
   {
     float ia[6], iv[6], x6[6];
@@ -1169,10 +1188,10 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
     qc[CC][0] = qc[CC][1] = qc[CC][2] = 0.f;
     if (lc < RC) {
       float x[3];
-      mat3vec(R0, M->cpoint[lc], x);
+      mat3vec(R0, rcand + 4 * lc, x);
 #pragma unroll
       for (int f = 0; f < 3; ++f) qc[CC][f] = s.p[f] + x[f];
-      qr[CC] = M->cradius[lc];
+      qr[CC] = rcand[4 * lc + 3];
     }
     // the queries the block summary cannot rule out (gs_terrain::may_contact: sphere_contact's own first test) go
     // into one list for the whole wave -- typically a minority (knees, the base, lifted feet end here) -- and the
@@ -1645,8 +1664,8 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
 #pragma unroll
   for (int j = 0; j < RC; ++j) {
     float x[3];
-    mat3vec(R0, M->cpoint[j], x);
-    const float r = M->cradius[j];
+    mat3vec(R0, rcand + 4 * j, x);
+    const float r = rcand[4 * j + 3];
     float dist, rmu_s = P.ground_mu;
     float rdir[3][3];
     if constexpr (TERR) {
@@ -2399,10 +2418,10 @@ __device__ __forceinline__ void substep_team(const DevModel* __restrict__ Min, c
 }
 
 template <class T>
-__device__ __forceinline__ void team_com_velocity(const DevModel* __restrict__ M, const TeamState<T>& s, float* v) {
+__device__ __forceinline__ void team_com_velocity(const float* __restrict__ sct, const TeamState<T>& s, float* v) {
   float R[9], c[3], wc[3];
   quat_to_mat(s.quat, R);
-  mat3vec(R, M->root_com, c);
+  mat3vec(R, sct + ShapeTab<T>::RCOM, c);
   cross3(s.w, c, wc);
   v[0] = s.vo[0] + wc[0]; v[1] = s.vo[1] + wc[1]; v[2] = s.vo[2] + wc[2];
 }
@@ -2451,25 +2470,29 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_simulate_team(con
   // from LDS instead of device memory every substep: [shape][team]
   __shared__ float mu_tab[T::NS * kTeamsPerBlock];
   __shared__ float stash_tab[team_stash_size<T>() * kTeamBlock];
+  const TeamLane tl = team_lane<T, EPW, ROWL>(B.N);
+  const int lc = tl.lc, e = tl.e, col = tl.col;
+  const int N = B.N;
+  // what the launch reads of its env (the state, the torques) is loaded first, by the lanes that stay (off lanes have
+  // e = N): the loads are in flight while the model is staged, and past the barrier the kernel loads nothing
+  TeamState<T> s;
+  float tau[CL];
+  if (e < N) {
+    team_load<T>(B.state, N, e, lc, s);
+#pragma unroll
+    for (int k = 0; k < CL; ++k) tau[k] = tau_aos ? tau_aos[(size_t)e * ND + lc * CL + k] : 0.f;
+  }
   stage_chain_model<T>(M, mdl);
   stage_shape_consts<T>(M, sct);
   // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
   // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
-  const TeamLane tl = team_lane<T, EPW, ROWL>(B.N);
-  const int lc = tl.lc, e = tl.e, col = tl.col;
   if (tl.on)
     for (int sh = lc; sh < T::NS; sh += LN)
-      mu_tab[sh * kTeamsPerBlock + (col >> 2)] = e < B.N ? B.mu[(size_t)sh * B.N + e] : 1.f;
+      mu_tab[sh * kTeamsPerBlock + (col >> 2)] = e < N ? B.mu[(size_t)sh * N + e] : 1.f;
   __syncthreads();
-  if (e >= B.N) return;
+  if (e >= N) return;
   const float* mu_t = mu_tab + (col >> 2);
   float* shw_wave = shw_tab + tl.wave * (shw_size<T>() / WaveForm<EPW>::WAVES);
-  const int N = B.N;
-  TeamState<T> s;
-  team_load<T>(B.state, N, e, lc, s);
-  float tau[CL];
-#pragma unroll
-  for (int k = 0; k < CL; ++k) tau[k] = tau_aos ? tau_aos[(size_t)e * ND + lc * CL + k] : 0.f;
   float* own = rows + col;
   const float* team = rows + (col & ~(LN - 1));
   GS_PROF_DECL
@@ -2492,42 +2515,71 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
   // the team's shape friction (constant over the launch), read by the contact records and the self-contact pool
   // from LDS instead of device memory every substep: [shape][team]
   __shared__ float mu_tab[T::NS * kTeamsPerBlock];
-  __shared__ float stash_tab[team_stash_size<T>() * kTeamBlock];
-  stage_chain_model<T>(M, mdl);
-  stage_shape_consts<T>(M, sct);
-  // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
-  // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
+  // The lane's CL raw action words are loaded once and held for the launch (every PD evaluation and the actions
+  // copy use them): in registers in the plane forms, in CL more slots of the lane's stash column in the TERR forms,
+  // which are at their register limit
+  constexpr bool kActRegs = !TERR;
+  constexpr int kActSlot = team_stash_size<T>();
+  __shared__ float stash_tab[(team_stash_size<T>() + (kActRegs ? 0 : CL)) * kTeamBlock];
+  __shared__ float dpos_tab[ND];  // A.default_pos
   const TeamLane tl = team_lane<T, EPW, ROWL>(B.N);
   const int lc = tl.lc, e = tl.e, col = tl.col;
+  const int N = B.N;
+  // this lane's first dof in the AoS tensors (formed where each use needs it, opaque_index)
+  auto dof0 = [&]() { return (size_t)opaque_index(e) * ND + lc * CL; };
+  // what the launch reads of its env (the state, the first evaluation's dof tensor, the actions) is loaded first, by
+  // the lanes that stay (off lanes have e = N): the loads are in flight while the model is staged, and past the
+  // barrier the kernel loads nothing from device memory but a TERR form's terrain
+  TeamState<T> s;
+  float q_in[CL], qd_in[CL];
+  [[maybe_unused]] float act[CL];
+  if (e < N) {
+    team_load<T>(B.state, N, e, lc, s);
+    const size_t d0 = dof0();
+#pragma unroll
+    for (int k = 0; k < CL; ++k) {
+      q_in[k] = A.dof_state_in[(d0 + k) * 2 + 0];
+      qd_in[k] = A.dof_state_in[(d0 + k) * 2 + 1];
+      const float aj = A.actions[d0 + k];
+      if constexpr (kActRegs) act[k] = aj;
+      else stash_tab[(kActSlot + k) * kTeamBlock + col] = aj;
+    }
+  }
+  stage_chain_model<T>(M, mdl);
+  stage_shape_consts<T>(M, sct);
+  for (int i = threadIdx.x; i < ND; i += blockDim.x) dpos_tab[i] = A.default_pos[i];
+  // (the workgroup's only barrier follows the staging: past it a wave's lanes beyond its EPW teams and the
+  // lanes of envs past N leave, and the waves that stay never wait for one another -- team_sync)
   if (tl.on)
     for (int sh = lc; sh < T::NS; sh += LN)
-      mu_tab[sh * kTeamsPerBlock + (col >> 2)] = e < B.N ? B.mu[(size_t)sh * B.N + e] : 1.f;
+      mu_tab[sh * kTeamsPerBlock + (col >> 2)] = e < N ? B.mu[(size_t)sh * N + e] : 1.f;
   __syncthreads();
-  if (e >= B.N) return;
+  if (e >= N) return;
   const float* mu_t = mu_tab + (col >> 2);
   float* shw_wave = shw_tab + tl.wave * (shw_size<T>() / WaveForm<EPW>::WAVES);
-  const int N = B.N;
-  TeamState<T> s;
-  team_load<T>(B.state, N, e, lc, s);
+  // the held action word k (TERR: out of the lane's own column, written by this lane or, row lanes, by its copies)
+  auto action = [&](int k) {
+    if constexpr (kActRegs) return act[k];
+    else return stash_tab[(kActSlot + k) * kTeamBlock + col];
+  };
   float tau[CL];
   float* own = rows + col;
   const float* team = rows + (col & ~(LN - 1));
   const int sub = P.substeps;
   const int n_pd = A.decimation * sub;
   const int total = (A.decimation + A.extra) * sub;
-  // this lane's first dof in the AoS tensors (formed where each use needs it, opaque_index)
-  auto dof0 = [&]() { return (size_t)opaque_index(e) * ND + lc * CL; };
   GS_PROF_DECL
+  // (the evaluation stays one site inside the loop: with the first one moved in front of the loop the compiler formed
+  // the substep's fused multiply-adds differently, measured -- the state a few ulp off the other forms')
   for (int it = 0; it < total; ++it) {
     if (it < n_pd && (it % sub) == 0) {
       const bool first = it == 0;
-      const size_t d0 = dof0();
 #pragma unroll
       for (int k = 0; k < CL; ++k) {
-        const float qj = first ? A.dof_state_in[(d0 + k) * 2 + 0] : s.q[k];
-        const float qdj = first ? A.dof_state_in[(d0 + k) * 2 + 1] : s.qd[k];
-        const float aj = A.actions[d0 + k];
-        tau[k] = clampf(A.kp * (A.scale * aj + A.default_pos[lc * CL + k] - qj) - A.kd * qdj, -A.tlim, A.tlim);
+        const float qj = first ? q_in[k] : s.q[k];
+        const float qdj = first ? qd_in[k] : s.qd[k];
+        const float aj = action(k);
+        tau[k] = clampf(A.kp * (A.scale * aj + dpos_tab[lc * CL + k] - qj) - A.kd * qdj, -A.tlim, A.tlim);
       }
     }
     // contact forces once per launch: every collecting substep stores the same words of cf_soa, so only those of the
@@ -2553,7 +2605,7 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
     for (int k = 0; k < CL; ++k) A.torques_out[d0 + k] = tau[k];
     if (A.actions_copy) {
 #pragma unroll
-      for (int k = 0; k < CL; ++k) A.actions_copy[d0 + k] = A.actions[d0 + k];
+      for (int k = 0; k < CL; ++k) A.actions_copy[d0 + k] = action(k);  // the raw words loaded
     }
   }
   if (A.root_out && lc == 0 && tl.out) {
@@ -2561,7 +2613,7 @@ __global__ __launch_bounds__(WaveForm<EPW>::THREADS, 1) void k_pd_step_team(cons
     o[0] = s.p[0]; o[1] = s.p[1]; o[2] = s.p[2];
     o[3] = s.quat[0]; o[4] = s.quat[1]; o[5] = s.quat[2]; o[6] = s.quat[3];
     float v[3];
-    team_com_velocity<T>(M, s, v);
+    team_com_velocity<T>(sct, s, v);
     o[7] = v[0]; o[8] = v[1]; o[9] = v[2];
     o[10] = s.w[0]; o[11] = s.w[1]; o[12] = s.w[2];
   }
