@@ -19,6 +19,8 @@
  *   rl_policy_head : the act forward's sampling / neglogp / value unnormalisation.
  *   rl_rollout_post : the rollout bookkeeping after each env step (play_steps).
  *   rl_rollout_pre : the experience slot written before each env step (play_steps).
+ *   rl_policy_infer / rl_play_post : the player (rl_games players.py): the whole policy forward in one launch, and
+ *            the per-step episode bookkeeping of BasePlayer.run.
  *
  * All pointers are device pointers; calls are ordered on `stream` (a hipStream_t,
  * NULL = legacy default stream) and return 0 on success, otherwise a nonzero
@@ -331,6 +333,48 @@ int rl_policy_kl_step(const void *mu_new, int32_t mu_half, const float *sigma_ne
                       int32_t sigma_is_log, float *mu_old, float *sigma_old, int32_t M, int32_t A, int32_t write_back,
                       float *kl, float *partials, int32_t adaptive, double kl_threshold, double *lr, float *opt_lr,
                       float *stats, const float *a_loss, const float *c_loss, const float *entropy, void *stream);
+
+/*
+ * The policy player (rl_infer.hip; rl_games players.py PpoPlayerContinuous).  Added under ABI 7: new entry points
+ * only, every earlier one unchanged, so a caller built against the earlier ABI 7 header keeps working.
+ *
+ * rl_policy_infer: the deterministic (or sampled) policy forward for num_envs rows in ONE launch:
+ *   1. y = clamp((x - float(mean)) / sqrt(float(var) + eps), -5, 5)   obs [N][obs_dim] f32; mean, var [obs_dim]
+ *      float64 (RunningMeanStd's frozen moments; both null: y = x)
+ *   2. num_layers (0 .. 4) hidden layers y = ELU(y W^T + b): W [out][in] f32 row-major and b [out] f32, the
+ *      nn.Linear parameters read in place; products and accumulation f32 (v_mfma_f32_16x16x4_f32, this kernel's
+ *      order of the sum), the bias added in f32 before ELU, ELU in f32
+ *   3. mu = y W_mu^T + b_mu (W_mu [A][last width], four f32 FMA chains over k mod 4 added pairwise, as rl_act_heads)
+ *   4. actions = mu (noise null) or noise * exp(logstd) + mu (rl_policy_head's f32 statements: the product rounded,
+ *      then the sum; noise [N][A] = torch's normal_ draws, logstd [A]); clip != 0: clamped to [-1, 1]
+ *   5. writes actions [N][A] and, where non-null, mu [N][A]; nothing else.
+ * `widths`, `weights` and `biases` are HOST arrays of num_layers entries (the pointers in them are device pointers).
+ * Limits: num_envs >= 1; 1 <= obs_dim <= 256 (any value); hidden widths multiples of 32, at most 512; at most 4
+ * layers; 1 <= num_actions <= 32.  Anything else returns nonzero, names the limit in rl_last_error() and writes
+ * nothing.  Any 4-byte aligned parameter pointer is taken (16-byte loads where a layer's rows allow them).
+ */
+#define RL_INFER_MAX_LAYERS 4
+#define RL_INFER_MAX_WIDTH 512
+#define RL_INFER_MAX_OBS 256
+#define RL_INFER_MAX_ACTIONS 32
+int rl_policy_infer(const float *obs, int32_t num_envs, int32_t obs_dim, const double *mean, const double *var,
+                    double eps, int32_t num_layers, const int32_t *widths, const float *const *weights,
+                    const float *const *biases, const float *w_mu, const float *b_mu, int32_t num_actions,
+                    const float *noise, const float *logstd, int32_t clip, float *actions, float *mu, void *stream);
+
+/*
+ * rl_play_post: the player's bookkeeping after one VecTask.step (rl_games players.py BasePlayer.run, the loop body
+ * after env_step), one launch, no host synchronisation.
+ *   rewards [N] f32; dones [N] (dones_bytes 1: bool / uint8, 8: int64)
+ *   state: cur_rewards, cur_steps [N] f32; sums [2] float64 = (sum_rewards, sum_steps); games [2] int64 =
+ *   (games_played, finished)
+ * In order: cur_rewards += r, cur_steps += 1; unless finished: the done envs' cur_rewards / cur_steps added to sums
+ * one by one in ascending env order (f32 operands widened, float64 sums) and their count to games_played (every env
+ * that finishes in the step that crosses games_num counts, as in rl_games); finished = 1 once games_played >=
+ * games_num; the done envs' counters zeroed.  Once finished is set, sums and games never change.
+ */
+int rl_play_post(const float *rewards, const void *dones, int32_t dones_bytes, int32_t num_envs, float *cur_rewards,
+                 float *cur_steps, double *sums, int64_t *games, int64_t games_num, void *stream);
 
 #ifdef __cplusplus
 }

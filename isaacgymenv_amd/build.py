@@ -22,7 +22,7 @@ LIBS = {
                      "gs_generic.hip", "gs_capi.hip"],
     "libgymtask.so": ["gt_anymal.hip", "gt_hound.hip", "gt_ant.hip"],
     "libgymrl.so": ["rl_gae.hip", "rl_grad.hip", "rl_rollout.hip", "rl_ppo_loss.hip", "rl_rms.hip", "rl_adam.hip", "rl_linear.hip",
-                   "rl_policy.hip"],
+                   "rl_policy.hip", "rl_infer.hip"],
 }
 # phase-profiling build of the simulator (tools/phase_profile.py); never loaded by default, built only
 # on request (`python -m isaacgymenv_amd.build --prof`)

@@ -5,6 +5,10 @@ the rl_games-compatible PPO learner (isaacgymenv_amd/rl).
     python -m isaacgymenvs.train task=AnymalTerrain headless=True [num_envs=4096] [max_iterations=N]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m isaacgymenvs.train task=AnymalTerrain multi_gpu=True headless=True
+    python -m isaacgymenvs.train task=Ant checkpoint=runs/Ant/nn/Ant.pth test=True num_envs=64
+
+test=True (reference train.py:205-216, 'play': cfg.test): no training; the checkpoint's policy plays
+``player.games_num`` episodes (rl/player.py) and the averages are printed.  Nothing is written.
 
 multi_gpu: one process per GPU (LOCAL_RANK -> cuda:k, rlgames_utils.py:53-127), seed + rank
 (train.py:120-123 via set_seed), torch.distributed over RCCL ("nccl"); each rank steps its own
@@ -33,8 +37,10 @@ def preprocess_train_config(cfg: dict, config_dict: dict) -> dict:
     return config_dict
 
 
-def launch(overrides: Optional[List[str]] = None, printer=print):
-    """Returns (agent, last epoch stats)."""
+def launch(overrides: Optional[List[str]] = None, printer=print, games_num: Optional[int] = None,
+           deterministic: Optional[bool] = None):
+    """Returns (agent, last epoch stats); with test=True, (player, the play run's stats).  ``games_num`` /
+    ``deterministic`` override the train config's ``player`` block (test=True only)."""
     import torch
     import torch.distributed as dist
 
@@ -45,6 +51,9 @@ def launch(overrides: Optional[List[str]] = None, printer=print):
     if cfg.get("task") is None or cfg.get("train") is None:
         raise ValueError("task=<Name> must name a task with a cfg/train/<Name>PPO.yaml")
     multi_gpu = bool(cfg["multi_gpu"])
+    test = bool(cfg.get("test"))
+    if test and multi_gpu:
+        raise ValueError("test=True plays a checkpoint on one GPU: multi_gpu=True is not supported with it")
     rank, local_rank = int(os.getenv("RANK", "0")), int(os.getenv("LOCAL_RANK", "0"))
     if multi_gpu and not dist.is_initialized():
         world = int(os.getenv("WORLD_SIZE", "1"))
@@ -70,11 +79,19 @@ def launch(overrides: Optional[List[str]] = None, printer=print):
     if cfg.get("max_iterations") not in ("", None):
         over["max_epochs"] = int(cfg["max_iterations"])
     pcfg = PpoConfig.from_train_cfg(train_cfg, **over)
+    if test:  # play: no learner, no training, no file written
+        from isaacgymenv_amd.rl import PpoPlayerContinuous
+        player = PpoPlayerContinuous(env, pcfg, device=rl_device, seed=seed,
+                                     player_cfg=train_cfg["params"]["config"].get("player"), games_num=games_num,
+                                     deterministic=deterministic)
+        if cfg.get("checkpoint"):
+            player.restore(cfg["checkpoint"])
+        return player, player.run(printer=printer)
     agent = A2CAgent(env, pcfg, device=rl_device, seed=seed)
     if cfg.get("checkpoint"):
         agent.restore(cfg["checkpoint"])
     stats = agent.train(pcfg.max_epochs, printer=printer)
-    if not cfg.get("test") and rank == 0:
+    if rank == 0:
         out = os.path.join("runs", pcfg.name, "nn", f"{pcfg.name}.pth")
         agent.save(out)
     return agent, stats

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = ["rl_abi_version", "rl_last_error", "rl_gae", "rl_splitk_accu
                     "rl_linear_bwd_g", "rl_kl_partials_size", "rl_policy_kl", "rl_adaptive_lr",
                     "rl_ppo_heads_partials_size", "rl_ppo_heads_loss", "rl_ppo_heads_loss_backward",
                     "rl_splitk_accum_multi", "rl_policy_kl_step", "rl_opt_step_h", "rl_rms_normalize_h", "rl_rollout_pre",
-                    "rl_linear_fwd_f32_g", "rl_act_heads"]
+                    "rl_linear_fwd_f32_g", "rl_act_heads", "rl_policy_infer", "rl_play_post"]
 _lib = None
 
 
@@ -131,6 +131,11 @@ def lib():
         L.rl_rollout_pre.restype = C.c_int
         L.rl_rollout_pre.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.rl_policy_infer.restype = C.c_int
+        L.rl_policy_infer.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.POINTER(C.c_int32),
+                                      C.POINTER(vp), C.POINTER(vp), vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]
+        L.rl_play_post.restype = C.c_int
+        L.rl_play_post.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp]
         L.rl_last_error.restype = C.c_char_p
         L.rl_abi_version.restype = C.c_int
         _lib = L
@@ -652,3 +657,107 @@ def opt_step_h(param, param_half, grad, exp_avg, exp_avg_sq, step, lr, scale, gr
                                scale.data_ptr() if scale is not None else None,
                                growth_tracker.data_ptr() if growth_tracker is not None else None, C.byref(hyper),
                                partials.data_ptr(), raw_stream()), "rl_opt_step_h")
+
+
+# ---------------------------------------------------------------- the policy player (rl_infer.hip)
+INFER_MAX_LAYERS, INFER_MAX_WIDTH, INFER_MAX_OBS, INFER_MAX_ACTIONS = 4, 512, 256, 32  # include/gymrl.h RL_INFER_*
+
+
+def policy_infer_fits(obs_dim: int, widths, num_actions: int) -> bool:
+    """The shapes rl_policy_infer takes (include/gymrl.h)."""
+    return (1 <= obs_dim <= INFER_MAX_OBS and len(widths) <= INFER_MAX_LAYERS and 1 <= num_actions <= INFER_MAX_ACTIONS
+            and all(32 <= w <= INFER_MAX_WIDTH and w % 32 == 0 for w in widths))
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def policy_infer(obs, num_envs: int, obs_dim: int, mean, var, eps: float, widths, weights, biases, w_mu, b_mu,
+                 num_actions: int, noise, logstd, clip: bool, actions, mu, check: bool = True) -> int:
+    """include/gymrl.h rl_policy_infer, argument for argument (tensors or None for the pointers; widths / weights /
+    biases: sequences, one entry per hidden layer).  Returns the kernel's return code; raises on nonzero with
+    ``check``.  Nothing is validated here: the C entry point owns the limits."""
+    n = len(widths)
+    c_widths = (C.c_int32 * max(n, 1))(*[int(w) for w in widths])
+    c_w = (C.c_void_p * max(n, 1))(*[_ptr(w) for w in weights])
+    c_b = (C.c_void_p * max(n, 1))(*[_ptr(b) for b in biases])
+    dev = actions.device if actions is not None else obs.device
+    rc = lib().rl_policy_infer(_ptr(obs), int(num_envs), int(obs_dim), _ptr(mean), _ptr(var), float(eps), n, c_widths,
+                               c_w, c_b, _ptr(w_mu), _ptr(b_mu), int(num_actions), _ptr(noise), _ptr(logstd),
+                               int(bool(clip)), _ptr(actions), _ptr(mu), raw_stream(dev))
+    if check and rc != 0:
+        raise RuntimeError(f"rl_policy_infer failed: {lib().rl_last_error().decode()}")
+    return rc
+
+
+class PolicyInfer:
+    """rl_policy_infer bound once to a model's parameters (read in place: the tensors must stay where they are; an
+    in-place load_state_dict keeps them).  layers: [(weight [out, in], bias [out])]; rms: the input RunningMeanStd or
+    None.  Call with obs [N, obs_dim] f32 contiguous on the parameters' GPU."""
+
+    def __init__(self, layers, w_mu, b_mu, logstd, rms=None):
+        ts = [t for wb in layers for t in wb] + [w_mu, b_mu, logstd]
+        dev = w_mu.device
+        assert all(t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in ts)
+        self.obs_dim = layers[0][0].shape[1] if layers else w_mu.shape[1]
+        self.widths = [w.shape[0] for w, _ in layers]
+        self.num_actions = w_mu.shape[0]
+        k = self.obs_dim
+        for (w, b), n in zip(layers, self.widths):
+            assert w.shape == (n, k) and b.shape == (n,)
+            k = n
+        assert w_mu.shape == (self.num_actions, k) and b_mu.numel() == self.num_actions
+        assert logstd.numel() == self.num_actions
+        if not policy_infer_fits(self.obs_dim, self.widths, self.num_actions):
+            raise ValueError("network outside rl_policy_infer's limits (include/gymrl.h)")
+        self._keep = ts
+        self.device = dev
+        n = len(layers)
+        self._n = n
+        self._widths = (C.c_int32 * max(n, 1))(*self.widths)
+        self._w = (C.c_void_p * max(n, 1))(*[w.data_ptr() for w, _ in layers])
+        self._b = (C.c_void_p * max(n, 1))(*[b.data_ptr() for _, b in layers])
+        self._mu = (w_mu.data_ptr(), b_mu.data_ptr())
+        self._logstd = logstd.data_ptr()
+        self._mean = self._var = None
+        self._eps = 0.0
+        if rms is not None:
+            m, v = rms.running_mean, rms.running_var
+            assert m.dtype == v.dtype == torch.float64 and m.numel() == v.numel() == self.obs_dim and m.device == dev
+            self._keep += [m, v]
+            self._mean, self._var, self._eps = m.data_ptr(), v.data_ptr(), float(rms.epsilon)
+        self._fn = lib().rl_policy_infer
+
+    def __call__(self, obs, noise=None, clip: bool = False, want_mu: bool = False):
+        """(actions [N, A], mu [N, A] or None).  noise: [N, A] f32 normal_ draws or None (actions = mu)."""
+        N = obs.shape[0]
+        A = self.num_actions
+        actions = torch.empty(N, A, dtype=torch.float32, device=self.device)
+        mu = torch.empty(N, A, dtype=torch.float32, device=self.device) if want_mu else None
+        rc = self._fn(obs.data_ptr(), N, self.obs_dim, self._mean, self._var, self._eps, self._n, self._widths,
+                      self._w, self._b, self._mu[0], self._mu[1], A, _ptr(noise), self._logstd, 1 if clip else 0,
+                      actions.data_ptr(), _ptr(mu), raw_stream(self.device))
+        if rc != 0:
+            raise RuntimeError(f"rl_policy_infer failed: {lib().rl_last_error().decode()}")
+        return actions, mu
+
+
+def play_post(rewards, dones, cur_rewards, cur_steps, sums, games, games_num: int, state_checked: bool = False) -> None:
+    """The player's bookkeeping after env.step as one kernel (include/gymrl.h rl_play_post).  rewards f32 [N]; dones
+    bool, uint8 or int64 [N]; cur_rewards, cur_steps f32 [N]; sums f64 [2] = (sum_rewards, sum_steps); games int64 [2]
+    = (games_played, finished).  state_checked: the caller's own state tensors passed these checks before."""
+    N = rewards.shape[0]
+    dev = rewards.device
+    if dones.dtype not in _FLAG_BYTES:
+        dones = dones.to(torch.uint8)
+    assert rewards.is_cuda and rewards.dtype == torch.float32 and rewards.is_contiguous()
+    assert dones.device == dev and dones.is_contiguous() and dones.numel() == N
+    if not state_checked:
+        for t, dt, n in ((cur_rewards, torch.float32, N), (cur_steps, torch.float32, N), (sums, torch.float64, 2),
+                         (games, torch.int64, 2)):
+            assert t.device == dev and t.dtype == dt and t.numel() == n and t.is_contiguous()
+    rc = lib().rl_play_post(rewards.data_ptr(), dones.data_ptr(), _FLAG_BYTES[dones.dtype], N, cur_rewards.data_ptr(),
+                            cur_steps.data_ptr(), sums.data_ptr(), games.data_ptr(), int(games_num), raw_stream(dev))
+    if rc != 0:
+        raise RuntimeError(f"rl_play_post failed: {lib().rl_last_error().decode()}")
