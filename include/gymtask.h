@@ -39,6 +39,8 @@ typedef struct gt_torch_rand_plan {
 } gt_torch_rand_plan;
 
 typedef struct gt_anymal_params {
+    /* num_dofs: 10..16 -- the hip reward term reads the hip dofs 0, 3, 6, 9 (anymal_terrain.py:378) whatever
+     * hip_dofs holds, so every gt_anymal_* entry point refuses fewer than 10 */
     int32_t num_envs, num_dofs, num_bodies, num_obs;
     int32_t base_index;
     int32_t num_feet, feet_idx[4];
@@ -149,8 +151,10 @@ typedef struct gt_anymal_reset_draws {
 } gt_anymal_reset_draws;
 
 /* The trimesh terrain's part of reset_idx (ABI 2; custom origins, anymal_terrain.py:385-398 with
- * update_terrain_level :427-435): before the reset, an env that walked less than a quarter of its
- * commanded distance over the episode moves a level down, one that left its tile a level up
+ * update_terrain_level :427-435): before the reset, an env that walked less than
+ * 0.25 * max_episode_length_s * |C| moves a level down -- |C| is ONE number, torch.norm over the x, y commands of every
+ * env reset in this step (the reference's line has no dim; taken before any command is redrawn) -- and one that left
+ * its tile a level up
  * (clip >= 0, modulo env_rows; only when update_levels = init_done && curriculum), and takes the
  * origin terrain_origins[level][type]; the root then starts at base_init_state + origin with x, y
  * offset by U(-0.5, 0.5) draws (drawn after the dof draws, before the command draws).
@@ -174,7 +178,8 @@ typedef struct gt_anymal_terrain_reset {
  * set_*_tensor_indexed); episode_out[13] = mean over the flagged envs of each episode sum /
  * episode_length_s (extras["episode"], :416-420), sums then zeroed; the means are summed in a
  * fixed order (bit-identical run to run).  terrain: NULL for the plane, else the trimesh part above.  scratch: GT_ANYMAL_RESET_SCRATCH_WORDS(num_envs) words
- * of device memory, the first 16 zero-initialised (a counter the kernel re-arms). */
+ * of device memory, the first 16 zero-initialised (word 0 a counter, word 1 the flagged envs' command norm of a
+ * terrain reset; the kernels leave both zero again). */
 #define GT_ANYMAL_RESET_SCRATCH_WORDS(num_envs) (16 + (GT_ANYMAL_NUM_TERMS + 1) * (((num_envs) + 63) / 64))
 int gt_anymal_reset_flagged(const gt_anymal_params *p, const gt_anymal_buffers *b, int k,
                             const gt_anymal_reset_draws *draws, const struct gt_anymal_terrain_reset *terrain,

@@ -106,6 +106,43 @@ __global__ void __launch_bounds__(64 * GT_ANYMAL_NUM_TERMS) k_episode_sums(gt_an
   if (lane == 0) ep[term] = v;
 }
 
+// update_terrain_level's torch.norm(self.commands[env_ids, :2]) (anymal_terrain.py:432) has no dim: it is ONE number,
+// the Frobenius norm over the commands of every env reset in this step.  It must be taken before any wave of
+// k_reset_flagged overwrites its envs' commands, so it is a launch of its own (terrain resets with the curriculum
+// on only): one workgroup; a lane adds its envs tid, tid + 1024, ... in order (four per pass, their loads issued
+// together and independent of the mask words), then the butterfly and the 16 wave sums in wave order: the same
+// bits every run.
+__global__ void __launch_bounds__(1024) k_flagged_cmd_norm(int num_envs, const float* __restrict__ commands,
+                                                           const uint64_t* __restrict__ masks,
+                                                           float* __restrict__ out) {
+  __shared__ float part[16];
+  const int tid = threadIdx.x;
+  float v = 0.0f;
+  for (int e0 = 0; e0 < num_envs; e0 += 4096) {
+    float c0[4], c1[4];
+    unsigned long long m[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = e0 + i * 1024 + tid;
+      const bool in = e < num_envs;
+      c0[i] = in ? commands[(size_t)e * 4 + 0] : 0.0f;
+      c1[i] = in ? commands[(size_t)e * 4 + 1] : 0.0f;
+      m[i] = in ? masks[e >> 6] : 0ull;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if ((m[i] >> ((e0 + i * 1024 + tid) & 63)) & 1ull) v += c0[i] * c0[i] + c1[i] * c1[i];
+  }
+  v = wave_sum(v);
+  if ((tid & 63) == 0) part[tid >> 6] = v;
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.0f;
+    for (int i = 0; i < 16; ++i) t += part[i];
+    *out = sqrtf(t);
+  }
+}
+
 // reset_idx for the envs post_a flagged (anymal_terrain.py:384-425, plane terrain).  One lane
 // per env, one wave per workgroup; the rank of a flagged env among all flagged envs comes from
 // post_a's per-wave ballots (exclusive prefix of popcounts), so no compaction pass is needed.
@@ -189,8 +226,8 @@ __global__ void __launch_bounds__(64) k_reset_flagged(gt_anymal_params p, gt_any
         const float dx = root[0] - tr.env_origins[(size_t)e * 3 + 0];
         const float dy = root[1] - tr.env_origins[(size_t)e * 3 + 1];
         const float dist = sqrtf(dx * dx + dy * dy);
-        const float c0 = b.commands[(size_t)e * 4 + 0], c1 = b.commands[(size_t)e * 4 + 1];
-        const float cn = sqrtf(c0 * c0 + c1 * c1);
+        // over every flagged env, as the reference's line: k_flagged_cmd_norm left it in the counter block's word 1
+        const float cn = *reinterpret_cast<const float*>(done + 1);
         lvl -= (dist < cn * tr.max_episode_length_s * 0.25f) ? 1 : 0;
         lvl += (dist > tr.env_length / 2.0f) ? 1 : 0;
         lvl = (lvl < 0 ? 0 : lvl) % tr.env_rows;
@@ -287,7 +324,12 @@ __global__ void __launch_bounds__(64) k_reset_flagged(gt_anymal_params p, gt_any
       else
         ep_out[lane] = v * (1.0f / (float)p.num_envs);  // torch.mean(terrain_levels.float())
     }
-    if (lane == 0) __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0) {
+      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // (the norm's word: every wave read it before its counter add, so all are done with it)
+      if (has_terrain && tr.update_levels)
+        __hip_atomic_store(done + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 
@@ -463,6 +505,10 @@ int check_params(const gt_anymal_params* p, const gt_anymal_buffers* b) {
     g_err = "gt_anymal: invalid parameters";
     return -1;
   }
+  if (p->num_dofs < 10) {  // post_a_env reads dq[0], dq[3], dq[6], dq[9] unconditionally
+    g_err = "gt_anymal: num_dofs must be at least 10 (the hip reward term reads the hip dofs 0, 3, 6, 9)";
+    return -1;
+  }
   if (h && (h->num_shoulders < 0 || h->num_shoulders > 4 || !h->eef_state || !h->arm_commands || !h->pos_control ||
             !h->effort_control || h->num_actions != p->num_dofs + 6)) {
     g_err = "gt_anymal: invalid UsefulHound extension";
@@ -599,6 +645,10 @@ int gt_anymal_reset_flagged(const gt_anymal_params* p, const gt_anymal_buffers* 
   float* partial = static_cast<float*>(scratch) + 16;
   const gt_anymal_hound h = hound_of(b);
   const dim3 g((p->num_envs + 63) / 64), bl(64);
+  // word 1 of the scratch counter block: the flagged envs' command norm (zeroed again by k_reset_flagged)
+  if (terrain && terrain->update_levels)
+    hipLaunchKernelGGL(k_flagged_cmd_norm, dim3(1), dim3(1024), 0, (hipStream_t)stream, p->num_envs, b->commands,
+                       b->reset_masks, static_cast<float*>(scratch) + 1);
   if (b->hound)
     hipLaunchKernelGGL(k_reset_flagged<true>, g, bl, 0, (hipStream_t)stream, *p, *b, h, k, *d, tr, terrain != nullptr,
                        env_ids_out, episode_out, episode_length_s, partial, done);

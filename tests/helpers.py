@@ -875,3 +875,291 @@ def linear_fwd_tiles(c, f32=False):
 def linear_dx_tiles(c):
     big = (c["M"] // 128) * (c["K"] // 128) * c["G"]
     return big if big >= 256 else (c["M"] // 64) * (c["K"] // 128) * c["G"]
+
+
+# ---- the AnymalTerrain / UsefulHound tail kernels (test_task_oracle.py asserts what is claimed here;
+# ---- test_task_kernels_gpu.py relies on it)
+TAIL_KINDS = ("ordinary", "base_contact", "knee_one", "knee_many", "shoulder", "tie_norm", "tie_z", "stumble_one",
+              "stumble_many", "first_contact", "contact_zero_air", "small_cmd", "prog_at", "prog_below",
+              "timeout_reset", "heading_above_pi", "heading_below_minus_pi", "c2_high", "c2_low", "reward_clip",
+              "timeout_only")  # env e is of kind e % len(TAIL_KINDS)
+TAIL_MARGIN = 1e-3  # every kind keeps this relative distance from every threshold it does not sit on
+TAIL_T = 1000       # max_episode_length
+TAIL_HEADING_DIFF = {"heading_above_pi": 5.0, "heading_below_minus_pi": -4.0, "c2_high": 2.5, "c2_low": -2.5}
+TAIL_BODIES = dict(anymal=dict(nb=13, base=0, knees=(2, 5, 8, 11), feet=(3, 6, 9, 12)),
+                   hound=dict(nb=24, base=0, knees=(2, 5, 8, 11), feet=(3, 6, 9, 12), shoulders=(14, 15, 16, 17)))
+
+
+def tail_kinds(N):
+    return np.arange(N) % len(TAIL_KINDS)
+
+
+def tail_params(N, nd, hound=False, **over):
+    """gt_anymal_params as a dict (oracle/task_oracle.py; tests fill the ctypes struct from it): AnymalTerrain.yaml's
+    shape with every reward scale nonzero, so that every term counts."""
+    bd = TAIL_BODIES["hound" if hound else "anymal"]
+    na = nd + 6 if hound else nd
+    dt = 0.02
+    scales = dict(s_termination=-2.0, s_lin_vel_xy=3.0, s_lin_vel_z=-4.0, s_ang_vel_z=0.5, s_ang_vel_xy=-0.05,
+                  s_orient=-0.3, s_torque=-0.00002, s_joint_acc=-0.0005, s_base_height=-0.7, s_air_time=1.0,
+                  s_collision=-1.0, s_stumble=-2.0, s_action_rate=-0.01, s_hip=-0.2)
+    leg = [0.03, 0.4, -0.8, 0.03, -0.4, 0.8, -0.03, 0.4, -0.8, -0.03, -0.4, 0.8, 0.1, -0.1, 0.2, -0.2]
+    p = dict(num_envs=N, num_dofs=nd, num_bodies=bd["nb"], num_obs=12 + 2 * nd + 140 + na + (10 if hound else 0),
+             base_index=bd["base"], num_feet=4, feet_idx=list(bd["feet"]), num_knees=4, knee_idx=list(bd["knees"]),
+             hip_dofs=[0, 3, 6, 9], allow_knee_contacts=0, max_episode_length=TAIL_T, dt=dt,
+             lin_vel_scale=2.0, ang_vel_scale=0.25, dof_pos_scale=1.0, dof_vel_scale=0.05, height_meas_scale=5.0,
+             default_dof_pos=leg[:nd] + [0.0] * (16 - nd),
+             base_init_state=[0.0, 0.0, 0.62, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0])
+    p.update({k: v * dt for k, v in scales.items()})
+    p.update(over)
+    return p
+
+
+def tail_hound(N, seed=0, num_shoulders=4):
+    """The gt_anymal_hound fields the statements read (oracle/task_oracle.py), with eef [N][13] rigid-body rows."""
+    rng = np.random.RandomState(8500 + seed)
+    return dict(num_actions=18, num_shoulders=num_shoulders, shoulder_idx=list(TAIL_BODIES["hound"]["shoulders"]),
+                arm_default=[0.0, 0.5, -0.5, 0.0, 0.3, 0.0], arm_lower=[-0.2, 0.3, -0.7, -0.2, 0.1, -0.2],
+                arm_upper=[0.2, 0.7, -0.3, 0.2, 0.5, 0.2], arm_noise2=1.0,
+                eef_rows=rng.normal(size=(N, 13)).astype(np.float32),
+                arm_commands=rng.uniform(-1, 1, (N, 3)).astype(np.float32))
+
+
+def _quat_rotate64(q, v):
+    u, w = q[:, :3], q[:, 3:4]
+    t = 2.0 * np.cross(u, v)
+    return v + w * t + np.cross(u, t)
+
+
+def tail_inputs(N, nd, seed=0, hound=False):
+    """(params, bufs, kinds) for gt_anymal_post_physics_a / _b: env e is of kind TAIL_KINDS[e % K].  Every env tracks
+    its command (reward decisively positive) with small torques, small forces on every body and feet either loaded
+    (fz 2..50) or free; on top of that, per kind: the base at (0, 0, 3); knee 0 / every knee at (0, 2, 0); a shoulder
+    at (2, 0, 0) (terminates only in the Hound form); base and knee 0 at exactly (0, 1, 0) (norm 1.0: no contact);
+    every foot at exactly (0, 0, 1) (neither contact nor stumble); foot 0 / every foot at (4, 4, +-0.5) (stumble);
+    every foot loaded with air time 0.3 / with air time 0; |command| = 0.05 with first contacts (the air-time gate);
+    progress + 1 = T - 1 / T - 2; the time-out flag with a base contact / alone; command heading - heading =
+    TAIL_HEADING_DIFF (+5: beyond pi, wrapped; -4: below -pi, kept by C fmod and clamped at -1 where a floored
+    remainder gives +1; +-2.5: the clamp alone); torques of 2000 (the reward clips at 0).  All f32, timeout_buf bool."""
+    rng = np.random.RandomState(8000 + seed)
+    K = len(TAIL_KINDS)
+    kind = tail_kinds(N)
+    is_ = lambda name: kind == TAIL_KINDS.index(name)  # noqa: E731
+    p = tail_params(N, nd, hound)
+    bd = TAIL_BODIES["hound" if hound else "anymal"]
+    na, nb = (nd + 6 if hound else nd), bd["nb"]
+    root = np.zeros((N, 13))
+    root[:, 0:2] = rng.uniform(-2, 2, (N, 2))
+    root[:, 2] = rng.uniform(0.45, 0.65, N)
+    axis = rng.normal(size=(N, 3))
+    axis[:, 2] *= 0.0
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    tilt, yaw = rng.uniform(0, 0.25, N), rng.uniform(-3.0, 3.0, N)
+    qt = np.concatenate([axis * np.sin(tilt / 2)[:, None], np.cos(tilt / 2)[:, None]], 1)
+    qy = np.stack([np.zeros(N), np.zeros(N), np.sin(yaw / 2), np.cos(yaw / 2)], 1)
+    # q = yaw * tilt (Hamilton product, xyzw)
+    a, b = qy, qt
+    q = np.stack([a[:, 3] * b[:, 0] + a[:, 0] * b[:, 3] + a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1],
+                  a[:, 3] * b[:, 1] - a[:, 0] * b[:, 2] + a[:, 1] * b[:, 3] + a[:, 2] * b[:, 0],
+                  a[:, 3] * b[:, 2] + a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0] + a[:, 2] * b[:, 3],
+                  a[:, 3] * b[:, 3] - a[:, 0] * b[:, 0] - a[:, 1] * b[:, 1] - a[:, 2] * b[:, 2]], 1)
+    root[:, 3:7] = q
+    va = rng.uniform(-np.pi, np.pi, N)
+    blv = np.concatenate([rng.uniform(0.3, 1.0, (N, 1)) * np.stack([np.cos(va), np.sin(va)], 1),
+                          rng.normal(0, 0.05, (N, 1))], 1)
+    blv[is_("small_cmd"), :2] = 0.05 * np.array([0.6, 0.8])
+    bav = np.concatenate([rng.normal(0, 0.3, (N, 2)), rng.uniform(-0.4, 0.4, (N, 1))], 1)
+    root[:, 7:10] = _quat_rotate64(q, blv)
+    root[:, 10:13] = _quat_rotate64(q, bav)
+    root = root.astype(np.float32)
+    q32 = root[:, 3:7].astype(np.float64)
+    fwd = _quat_rotate64(q32, np.tile([1.0, 0.0, 0.0], (N, 1)))
+    heading = np.arctan2(fwd[:, 1], fwd[:, 0])
+    diff = 2.0 * bav[:, 2] + rng.uniform(-0.02, 0.02, N)
+    for name, v in TAIL_HEADING_DIFF.items():
+        diff = np.where(is_(name), v + rng.uniform(-0.05, 0.05, N), diff)
+    cmd = np.zeros((N, 4))
+    cmd[:, :2] = blv[:, :2] + rng.uniform(-0.02, 0.02, (N, 2))
+    cmd[is_("small_cmd"), :2] = 0.05 * np.array([0.6, 0.8])
+    cmd[:, 2] = rng.uniform(-1, 1, N)
+    cmd[:, 3] = heading + diff
+    cf = rng.uniform(-0.2, 0.2, (N, nb, 3))
+    feet, knees = list(bd["feet"]), list(bd["knees"])
+    loaded = rng.rand(N, 4) < 0.5
+    air = np.where(rng.rand(N, 4) < 0.5, rng.uniform(0.02, 0.6, (N, 4)), 0.0)
+    for k in range(4):
+        cf[:, feet[k], 2] = np.where(loaded[:, k], rng.uniform(2.0, 50.0, N), cf[:, feet[k], 2])
+    cf[is_("base_contact") | is_("timeout_reset"), bd["base"]] = [0.0, 0.0, 3.0]
+    cf[is_("knee_one"), knees[0]] = [0.0, 2.0, 0.0]
+    for k in knees:
+        cf[is_("knee_many"), k] = [0.0, 2.0, 0.0]
+    cf[is_("shoulder"), TAIL_BODIES["hound"]["shoulders"][1] if hound else 1] = [2.0, 0.0, 0.0]
+    cf[is_("tie_norm"), bd["base"]] = [0.0, 1.0, 0.0]
+    cf[is_("tie_norm"), knees[0]] = [0.0, 1.0, 0.0]
+    for k in range(4):
+        cf[is_("tie_z"), feet[k]] = [0.0, 0.0, 1.0]
+        cf[is_("stumble_many"), feet[k]] = [4.0, 4.0, -0.5 if k % 2 else 0.5]
+        m = is_("first_contact") | is_("contact_zero_air") | is_("small_cmd")
+        cf[m, feet[k], 2] = 3.0 + k
+        air[is_("first_contact") | is_("small_cmd"), k] = 0.3 + 0.1 * k
+        air[is_("contact_zero_air"), k] = 0.0
+    cf[is_("stumble_one"), feet[0]] = [4.0, 4.0, 0.5]
+    tq = rng.uniform(-20, 20, (N, na))
+    tq[is_("reward_clip")] = 2000.0
+    act = rng.uniform(-1, 1, (N, na))
+    lact = act + rng.uniform(-0.2, 0.2, (N, na))
+    dof = np.zeros((N, na, 2))
+    default = np.asarray(p["default_dof_pos"])[:nd]
+    dof[:, :nd, 0] = default + rng.uniform(-0.2, 0.2, (N, nd))
+    dof[:, nd:, 0] = rng.uniform(-0.5, 0.5, (N, na - nd))
+    dof[:, :, 1] = rng.normal(0, 1.0, (N, na))
+    lqd = dof[:, :nd, 1] + rng.normal(0, 0.5, (N, nd))
+    prog = rng.randint(0, TAIL_T - 100, N).astype(np.int64)
+    prog[is_("prog_at")] = TAIL_T - 2
+    prog[is_("prog_below")] = TAIL_T - 3
+    timeout = is_("timeout_reset") | is_("timeout_only")
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float32)  # noqa: E731
+    bufs = dict(root_states=root, contact_forces=f(cf), dof_state=f(dof), torques=f(tq), actions=f(act),
+                last_actions=f(lact), last_dof_vel=f(lqd), commands=f(cmd), feet_air_time=f(air), progress_buf=prog,
+                randomize_buf=rng.randint(0, 5000, N).astype(np.int64), timeout_buf=timeout.copy(),
+                reset_buf=np.zeros(N, dtype=np.uint8), episode_sums=tail_episode_sums(N, seed),
+                noise_scale=f(rng.uniform(0.0, 0.2, p["num_obs"])), clip_obs=np.inf, measured_heights=None)
+    assert K == len(TAIL_KINDS)
+    return p, bufs, kind
+
+
+def tail_episode_sums(N, seed=0):
+    """episode_sums [13][N] f32 ~ N(0, 0.5) (tail_inputs' own; seeds 0..15 give the err_f32 of episode_out)."""
+    return np.random.RandomState(8100 + seed).normal(0, 0.5, (13, N)).astype(np.float32)
+
+
+def tail_heights(N, seed=0):
+    """measured_heights [N][140] for post_b: root z - 0.5 - h runs from about -1.6 to 1.6, so the +-1 clip binds on
+    both sides and not at all."""
+    rng = np.random.RandomState(8700 + seed)
+    return rng.uniform(-1.5, 1.5, (N, 140)).astype(np.float32)
+
+
+def reset_masks_cases(N):
+    """{name: uint64 mask words [ceil(N / 64)]}, hand-built (not made by post_a): none, all, first, last, alternating
+    and, for N > 4096 (more than 64 words: the second pass of the prefix and of the staging loop), flagged envs in
+    the last wave only and in the first and last waves.  Bits at and beyond N are 0."""
+    W = (N + 63) // 64
+    full = lambda n: np.uint64((1 << n) - 1)  # noqa: E731
+    allm = np.full(W, np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
+    allm[W - 1] = full(N - 64 * (W - 1))
+    one = lambda e: np.uint64(1) << np.uint64(e & 63)  # noqa: E731
+    first, last = np.zeros(W, np.uint64), np.zeros(W, np.uint64)
+    first[0] = one(0)
+    last[(N - 1) >> 6] = one(N - 1)
+    cases = dict(none=np.zeros(W, np.uint64), all=allm, first=first, last=last,
+                 alternating=allm & np.uint64(0x5555555555555555))
+    if N > 4096:
+        lw = np.zeros(W, np.uint64)
+        lw[W - 1] = allm[W - 1]
+        fl = lw.copy()
+        fl[0] = np.uint64(0x8000000000000421)
+        cases.update(last_wave=lw, first_and_last_wave=fl)
+    return cases
+
+
+def popcount(masks):
+    return int(sum(bin(int(w)).count("1") for w in np.asarray(masks).view(np.uint64)))
+
+
+def reset_draws(k, nd, seed=0, terrain=False, hound=False):
+    """The uniforms of one reset (u_pos, u_vel [k][nd], u_cmd_* [k], u_root_xy [k][2], u_arm [k][6]) and
+    AnymalTerrain's torch_rand_float maps.  Every fourth row draws a command below the 0.25 gate; u_arm's rows run
+    through 0.02 and 0.98 (the arm clamp at both limits with tail_hound's arm_noise2 = 1 and limits of +-0.2)."""
+    rng = np.random.RandomState(8800 + seed)
+    u = lambda *s: rng.uniform(0.0, 1.0, s).astype(np.float32)  # noqa: E731
+    d = dict(u_pos=u(k, nd), u_vel=u(k, nd), u_cmd_x=u(k), u_cmd_y=u(k), u_cmd_h=u(k),
+             pos_range=1.0, pos_lower=0.5, vel_range=0.2, vel_lower=-0.1, cmd_x_range=2.0, cmd_x_lower=-1.0,
+             cmd_y_range=2.0, cmd_y_lower=-1.0, cmd_h_range=6.28, cmd_h_lower=-3.14)
+    small = np.arange(k) % 4 == 1
+    d["u_cmd_x"][small] = np.float32(0.55)  # (0.1, 0.06): norm 0.117 < 0.25
+    d["u_cmd_y"][small] = np.float32(0.53)
+    extra = {}
+    if terrain:
+        extra["u_root_xy"] = u(k, 2)
+    if hound:
+        ua = u(k, 6)
+        ua[np.arange(k) % 3 == 0] = np.float32(0.02)
+        ua[np.arange(k) % 3 == 1] = np.float32(0.98)
+        extra["u_arm"] = ua
+    return d, extra
+
+
+TERRAIN_STATES = 7  # odd: the alternating mask reaches every state
+
+
+def terrain_reset_inputs(N, ids=None, seed=0, update_levels=1, batch_norm=0.4):
+    """gt_anymal_terrain_reset's fields for N envs on a 5 x 3 tile grid (env_length 8: a tile is left beyond 4 m; 20 s
+    episodes) for a reset of the envs `ids` (default: all).  The commands of the envs in `ids` have norm
+    batch_norm / sqrt(len(ids)) each, so that torch.norm over all of them is batch_norm and the level-down threshold
+    0.25 * 20 * batch_norm: 2 m at 0.4 (below the tile's 4 m), 10 m at 2.0 (beyond it: every env that leaves its tile
+    also moves down, net 0).  Every other env commands 10 m/s: counting it would put the threshold beyond any walk.
+    Env e is of state e % 7 by the distance it walked from its origin -- 0: 0.05 m (down); 1: 0.05 m on level 0 (clip
+    at 0); 2: 5 m (up, or net 0); 3: 5 m on the top level (wraps to 0, or net 0); 4: 3 m (neither, or down);
+    5: 1 m (down by the batch's norm; by its own command's, 5 * batch_norm / sqrt(k), only for k < 5); 6: as 0.
+    Returns (fields, root_xy [N][2], cmd_xy [N][2], state); root x, y and commands go into the buffers."""
+    rng = np.random.RandomState(8900 + seed)
+    rows, cols = 5, 3
+    state = np.arange(N) % TERRAIN_STATES
+    ids = np.arange(N) if ids is None else np.asarray(ids)
+    levels = rng.randint(1, rows - 1, N).astype(np.int64)
+    levels[state == 1] = 0
+    levels[state == 3] = rows - 1
+    types = rng.randint(0, cols, N).astype(np.int64)
+    to = rng.uniform(-20, 20, (rows, cols, 3)).astype(np.float32)
+    eo = to[levels, types].copy()
+    walked = np.select([state == 0, state == 1, state == 2, state == 3, state == 4], [0.05, 0.05, 5.0, 5.0, 3.0], 1.0)
+    ang = rng.uniform(-3, 3, N)
+    root_xy = eo[:, :2] + walked[:, None] * np.stack([np.cos(ang), np.sin(ang)], 1)
+    cmd_xy = np.tile([6.0, 8.0], (N, 1))
+    ca = rng.uniform(-3, 3, len(ids))
+    cmd_xy[ids] = batch_norm / np.sqrt(max(len(ids), 1)) * np.stack([np.cos(ca), np.sin(ca)], 1)
+    t = dict(terrain_levels=levels, terrain_types=types, env_origins=eo, terrain_origins=to, env_rows=rows,
+             env_cols=cols, update_levels=update_levels, env_length=8.0, max_episode_length_s=20.0, xy_range=1.0,
+             xy_lower=-0.5)
+    return t, root_xy.astype(np.float32), cmd_xy.astype(np.float32), state
+
+
+HEIGHTS_SHAPES = ((1, 1), (3, 140), (37, 7))  # (N, num_points)
+HEIGHTS_MAP = dict(rows=48, cols=37, border=1.0, hs=0.1, vs=0.005)
+HEIGHTS_NEAR = 1e-4  # cells: closer to an integer, f32 may truncate to either neighbour
+
+
+def heights_inputs(N, num_points, seed=0):
+    """(samples int16 [48][37] with distinct values, border, hs, vs, root_states [N][13], points [N][np][3]).  Probe
+    (e, k) is of kind (e * np + k) % 7 by where it lands before clipping: 0-1 the interior; 2-5 up to 3 cells beyond
+    the x-low, x-high, y-low, y-high border of the map; 6: within one cell below 0 after the border shift (truncation
+    goes to cell 0, toward zero).  Envs alternate yaw-only and full (tilted) quaternions; the kernel and the reference
+    use the yaw of (0, 0, qz, qw) normalised either way."""
+    rng = np.random.RandomState(9900 + seed)
+    m = HEIGHTS_MAP
+    rows, cols, border, hs = m["rows"], m["cols"], m["border"], m["hs"]
+    samples = (rng.permutation(rows * cols).astype(np.int64) - rows * cols // 2).astype(np.int16).reshape(rows, cols)
+    root = np.zeros((N, 13))
+    root[:, 0] = rng.uniform(0.5, rows * hs - 2 * border + 0.5, N)
+    root[:, 1] = rng.uniform(0.5, cols * hs - 2 * border + 0.5, N)
+    root[:, 2] = 0.6
+    yaw = rng.uniform(-3.1, 3.1, N)
+    qz, qw = np.sin(yaw / 2), np.cos(yaw / 2)
+    full = np.arange(N) % 2 == 1
+    root[:, 3] = np.where(full, 0.2, 0.0)
+    root[:, 4] = np.where(full, -0.1, 0.0)
+    s = np.sqrt(1.0 - root[:, 3] ** 2 - root[:, 4] ** 2)
+    root[:, 5], root[:, 6] = qz * s, qw * s
+    kindp = (np.arange(N * num_points) % 7).reshape(N, num_points)
+    X, Y = rows * hs, cols * hs  # the map's extent in shifted coordinates
+    u = lambda: rng.uniform(0, 1, (N, num_points))  # noqa: E731
+    tx = np.select([kindp == 2, kindp == 3, kindp == 6], [-3 * hs * u(), X + 3 * hs * u(), -hs * (0.05 + 0.9 * u())],
+                   X * u())
+    ty = np.select([kindp == 4, kindp == 5, kindp == 6], [-3 * hs * u(), Y + 3 * hs * u(), -hs * (0.05 + 0.9 * u())],
+                   Y * u())
+    # world target = shifted - border; the probe in the base's yaw frame
+    dx, dy = tx - border - root[:, 0:1], ty - border - root[:, 1:2]
+    c, sn = np.cos(yaw)[:, None], np.sin(yaw)[:, None]
+    pts = np.stack([c * dx + sn * dy, -sn * dx + c * dy, rng.uniform(-0.1, 0.1, (N, num_points))], -1)
+    return (samples, border, hs, m["vs"], root.astype(np.float32), np.ascontiguousarray(pts, dtype=np.float32), kindp)
