@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GT_ABI_VERSION 5
+#define GT_ABI_VERSION 6
 #define GT_ANYMAL_NUM_TERMS 13  /* lin_vel_xy lin_vel_z ang_vel_z ang_vel_xy orient torques joint_acc
                                    base_height air_time collision stumble action_rate hip */
 
@@ -58,6 +58,7 @@ typedef struct gt_anymal_params {
 } gt_anymal_params;
 
 struct gt_anymal_hound;
+struct gt_anymal_variant;
 
 typedef struct gt_anymal_buffers {
     float *root_states;          /* [N][13]                                   */
@@ -98,7 +99,25 @@ typedef struct gt_anymal_buffers {
     const struct gt_anymal_hound *hound; /* NULL for AnymalTerrain; UsefulHound's differences (ABI 3) */
     float *obs_mirror;           /* ABI 5: [N][num_obs] or NULL: a second copy of what obs_out receives (a
                                     learner's static act-forward input: no copy launch per step); needs obs_out */
+    const struct gt_anymal_variant *variant; /* ABI 6: NULL for AnymalTerrain and UsefulHound; a task that is
+                                    AnymalTerrain with another robot (HoundTerrain) */
 } gt_anymal_buffers;
+
+/* ABI 6: a task that runs AnymalTerrain's tail on the plane with its own termination rule and base-height target
+ * (HoundTerrain, reference tasks/Hound_terrain.py; every gt_anymal_* entry point takes it through
+ * gt_anymal_buffers.variant, and refuses it together with `hound`):
+ *   - check_termination (:304-310): contacts on the term_link_idx links (the four shoulders) terminate, and with
+ *     knees_terminate so do the knee_idx links (the thighs) whatever allow_knee_contacts says;
+ *   - compute_reward (:347): base_height = square(z - base_height_target) * s_base_height (AnymalTerrain: 0.52);
+ *     the collision term counts the knee_idx links only, as AnymalTerrain's.
+ * The reset and the observations are AnymalTerrain's own.  The extra contact rows are read only with a variant:
+ * the kernels without one are the same instantiations as before.  gymsim's in-kernel tail (gs_pd_args.tail_*) has
+ * no variant form and refuses one. */
+typedef struct gt_anymal_variant {
+    float base_height_target;
+    int32_t knees_terminate;
+    int32_t num_term_links, term_link_idx[4];
+} gt_anymal_variant;
 
 /* UsefulHound (reference tasks/useful_hound.py) runs the same tail with these differences
  * (ABI 3; the gt_anymal_* entry points take them through gt_anymal_buffers.hound):

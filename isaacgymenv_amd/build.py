@@ -34,7 +34,7 @@ SIM_FLAGS = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"libgymtask.so": ["-ffp-contract=off"], "libgymrl.so": ["-ffp-contract=off"], "libgymsim.so": SIM_FLAGS,
                "libgymsim_prof.so": SIM_FLAGS + ["-DGS_PHASE_PROFILE"]}
 HEADERS = ["gs_internal.h", "gs_topologies.h", "gs_math.h", "gs_terrain.h", "gs_pairs.h", "gs_solver.h", "gs_kinematics.h", "gs_host_impl.h",
-           "gs_physics_impl.h", "torch_philox.h"]
+           "gs_physics_impl.h", "torch_philox.h", "gt_anymal_tail.h"]
 # gs_phys_inst.hip is compiled once per (topology, kernel form): 0 simulate plane, 1 simulate terrain-mesh,
 # 2 fused PD step plane, 3 fused PD step terrain-mesh (gs_physics_impl.h)
 INST_SRC = "gs_phys_inst.hip"
@@ -72,6 +72,8 @@ def _stale(out: str, srcs) -> bool:
     # each library implements one public header (the others do not affect it)
     header = {"gs_": "gymsim.h", "gt_": "gymtask.h", "rl_": "gymrl.h"}[srcs[0][:3]]
     deps.append(os.path.join(os.path.dirname(HERE), "include", header))
+    if header == "gymsim.h":  # the lane-team kernel's in-kernel tail takes libgymtask's structs (gs_pd_args.tail_*)
+        deps.append(os.path.join(os.path.dirname(HERE), "include", "gymtask.h"))
     deps.append(os.path.abspath(__file__))  # flags live here
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
@@ -108,6 +110,8 @@ def build(force: bool = False, verbose: bool = True, prof: bool = False, variant
         header = {"gs_": "gymsim.h", "gt_": "gymtask.h", "rl_": "gymrl.h"}[srcs[0][:3]]
         common = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__),
                                                               os.path.join(os.path.dirname(HERE), "include", header)]
+        if header == "gymsim.h":
+            common.append(os.path.join(os.path.dirname(HERE), "include", "gymtask.h"))
         objs = []
         for src in srcs:
             for suffix, defs in _units(src):

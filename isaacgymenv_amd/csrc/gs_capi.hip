@@ -25,9 +25,13 @@ namespace {
 thread_local std::string g_err;
 
 int fail(const char* fmt, const char* arg = nullptr) {
-  char buf[512];
-  std::snprintf(buf, sizeof(buf), fmt, arg ? arg : "");
-  g_err = buf;
+  // sized to the message: a topology signature runs to several hundred characters (Hound_new: 84 candidates, 17
+  // links), and the reason that follows it must not be cut off
+  const char* a = arg ? arg : "";
+  const int n = std::snprintf(nullptr, 0, fmt, a);
+  std::string s(n > 0 ? (size_t)n : 0, '\0');
+  if (n > 0) std::snprintf(&s[0], (size_t)n + 1, fmt, a);
+  g_err = s;
   return -1;
 }
 int hip_fail(hipError_t e, const char* where) {
@@ -830,6 +834,9 @@ int gs_sim_pd_step(gs_sim* s, const gs_pd_args* a, void* stream) {
     const gt_anymal_buffers* tb = a->tail_buffers;
     auto aligned = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
     if (!gs_sim_pd_tail_supported(s)) return fail("gs_sim_pd_step: this sim's kernel has no fused tail");
+    if (tb && tb->variant)
+      return fail("gs_sim_pd_step: the in-kernel tail is AnymalTerrain's on the lane-team kernel; a gt_anymal_variant "
+                  "task runs libgymtask's launches");
     if (!tp || !tb || tb->hound || tp->num_envs != s->N || tp->num_dofs != s->nd || tp->num_dofs % 4 != 0 ||
         tp->num_bodies != s->nr || tp->num_feet > 4 || tp->num_knees > 4 || tp->num_feet < 0 || tp->num_knees < 0 ||
         tp->base_index < 0 || tp->base_index >= s->nr || !tb->reset_count || !tb->reset_masks || !tb->reset_buf ||

@@ -44,6 +44,20 @@ __global__ void __launch_bounds__(64) k_post_a(gt_anymal_params p, gt_anymal_buf
   }
 }
 
+// k_post_a with a gt_anymal_variant (gymtask.h ABI 6; post_a_env's VAR form): a kernel of its own, so that the
+// instantiations above keep their arguments and their code.
+template <bool VEC, int NDC = 0>
+__global__ void __launch_bounds__(64) k_post_a_var(gt_anymal_params p, gt_anymal_buffers b, gt_anymal_variant v) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  bool reset = false;
+  if (e < p.num_envs) reset = post_a_env<VEC, false, NDC, true>(p, b, gt_anymal_hound{}, e, v);
+  const unsigned long long m = __ballot(reset);
+  if ((threadIdx.x & 63) == 0) {
+    if (b.reset_masks) b.reset_masks[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = m;
+    publish_count(b, (unsigned)__popcll(m), (gridDim.x * blockDim.x + 63) / 64);
+  }
+}
+
 __global__ void k_reset(gt_anymal_params p, gt_anymal_buffers b, const int32_t* __restrict__ ids, int k,
                         const float* __restrict__ off, const float* __restrict__ vel, const float* __restrict__ cx,
                         const float* __restrict__ cy, const float* __restrict__ ch) {
@@ -425,13 +439,18 @@ __device__ __attribute__((noinline)) void post_b_elem_call(const gt_anymal_param
                                                            const gt_torch_rand_plan& plan, const int e, const int k) {
   post_b_elem<NOISE, false>(p, b, gt_anymal_hound{}, noise, plan, e, k);
 }
-template <int NOISE>
-__global__ void __launch_bounds__(256) k_post_ab(gt_anymal_params p, gt_anymal_buffers b,
-                                                 const float* __restrict__ noise, gt_torch_rand_plan plan) {
+// (VAR: with a gt_anymal_variant, k_post_ab_var below; k_post_ab is the VAR = false form, as before)
+template <int NOISE, bool VAR>
+__device__ __forceinline__ void post_ab_run(const gt_anymal_params& p, const gt_anymal_buffers& b,
+                                            const gt_anymal_variant& v, const float* __restrict__ noise,
+                                            const gt_torch_rand_plan& plan) {
   const gt_anymal_hound h{};
   const int tid = threadIdx.x, e0 = blockIdx.x * kAbEnvs, N = p.num_envs;
   bool reset = false;
-  if (tid < kAbEnvs && e0 + tid < N) reset = post_a_env<true, false, 12>(p, b, h, e0 + tid);
+  if (tid < kAbEnvs && e0 + tid < N) {
+    if constexpr (VAR) reset = post_a_env<true, false, 12, true>(p, b, h, e0 + tid, v);
+    else reset = post_a_env<true, false, 12>(p, b, h, e0 + tid);
+  }
   const unsigned long long m = __ballot(reset);  // (wave 0: lanes 0-15 hold the envs)
   if (tid == 0) {
     uint16_t* slices = reinterpret_cast<uint16_t*>(b.reset_masks);
@@ -443,6 +462,16 @@ __global__ void __launch_bounds__(256) k_post_ab(gt_anymal_params p, gt_anymal_b
   __syncthreads();
   const int no = p.num_obs, ne = (N - e0 < kAbEnvs ? N - e0 : kAbEnvs);
   for (int i = tid; i < ne * no; i += blockDim.x) post_b_elem_call<NOISE>(p, b, noise, plan, e0 + i / no, i % no);
+}
+template <int NOISE>
+__global__ void __launch_bounds__(256) k_post_ab(gt_anymal_params p, gt_anymal_buffers b,
+                                                 const float* __restrict__ noise, gt_torch_rand_plan plan) {
+  post_ab_run<NOISE, false>(p, b, gt_anymal_variant{}, noise, plan);
+}
+template <int NOISE>
+__global__ void __launch_bounds__(256) k_post_ab_var(gt_anymal_params p, gt_anymal_buffers b, gt_anymal_variant v,
+                                                     const float* __restrict__ noise, gt_torch_rand_plan plan) {
+  post_ab_run<NOISE, true>(p, b, v, noise, plan);
 }
 
 // get_heights, one lane per (env, probe).  The statement order follows the reference's torch
@@ -514,6 +543,21 @@ int check_params(const gt_anymal_params* p, const gt_anymal_buffers* b) {
     g_err = "gt_anymal: invalid UsefulHound extension";
     return -1;
   }
+  if (const gt_anymal_variant* v = b->variant) {
+    if (h) {
+      g_err = "gt_anymal: a gt_anymal_variant cannot be combined with the UsefulHound extension (hound): the variant "
+              "is AnymalTerrain's own tail with another termination rule";
+      return -1;
+    }
+    bool ok = v->num_term_links >= 0 && v->num_term_links <= 4 && v->base_height_target == v->base_height_target &&
+              p->base_index >= 0 && p->base_index < p->num_bodies;
+    for (int k = 0; ok && k < v->num_term_links; ++k)
+      ok = v->term_link_idx[k] >= 0 && v->term_link_idx[k] < p->num_bodies;
+    if (!ok) {
+      g_err = "gt_anymal: invalid gt_anymal_variant (at most 4 terminating links, each a row of contact_forces)";
+      return -1;
+    }
+  }
   return 0;
 }
 gt_anymal_hound hound_of(const gt_anymal_buffers* b) { return b->hound ? *b->hound : gt_anymal_hound{}; }
@@ -541,7 +585,13 @@ int gt_anymal_post_physics_a(const gt_anymal_params* p, const gt_anymal_buffers*
   const gt_anymal_hound h = hound_of(b);
   // (GT_POST_A_GENERIC set: the runtime-nd form, an A/B switch)
   static const bool generic = std::getenv("GT_POST_A_GENERIC") != nullptr;
-  if (b->hound) hipLaunchKernelGGL((k_post_a<false, true>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
+  if (b->variant) {  // (check_params refused it together with hound)
+    const gt_anymal_variant v = *b->variant;
+    if (vec && p->num_dofs == 12 && !generic)
+      hipLaunchKernelGGL((k_post_a_var<true, 12>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, v);
+    else if (vec) hipLaunchKernelGGL((k_post_a_var<true>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, v);
+    else hipLaunchKernelGGL((k_post_a_var<false>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, v);
+  } else if (b->hound) hipLaunchKernelGGL((k_post_a<false, true>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
   else if (vec && p->num_dofs == 12 && !generic)  // AnymalTerrain: straight-line loads (gt_anymal_tail.h NDC)
     hipLaunchKernelGGL((k_post_a<true, false, 12>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
   else if (vec) hipLaunchKernelGGL((k_post_a<true, false>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
@@ -589,7 +639,11 @@ int gt_anymal_post_physics_ab(const gt_anymal_params* p, const gt_anymal_buffers
   }
   const dim3 g((p->num_envs + kAbEnvs - 1) / kAbEnvs), bl(256);
   const gt_torch_rand_plan pl = noise_plan ? *noise_plan : gt_torch_rand_plan{};
-  if (noise_plan) hipLaunchKernelGGL((k_post_ab<2>), g, bl, 0, (hipStream_t)stream, *p, *b, nullptr, pl);
+  if (b->variant) {
+    const gt_anymal_variant v = *b->variant;
+    if (noise_plan) hipLaunchKernelGGL((k_post_ab_var<2>), g, bl, 0, (hipStream_t)stream, *p, *b, v, nullptr, pl);
+    else hipLaunchKernelGGL((k_post_ab_var<0>), g, bl, 0, (hipStream_t)stream, *p, *b, v, nullptr, pl);
+  } else if (noise_plan) hipLaunchKernelGGL((k_post_ab<2>), g, bl, 0, (hipStream_t)stream, *p, *b, nullptr, pl);
   else hipLaunchKernelGGL((k_post_ab<0>), g, bl, 0, (hipStream_t)stream, *p, *b, nullptr, pl);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail("gt_anymal_post_physics_ab", e);

@@ -97,11 +97,16 @@ constexpr int kMaxActions = 20;  // UsefulHound: 18
 // line code: guarded loads put the compiler's conservative vmcnt waits at each branch join, one memory round trip
 // per group (23 waits in the runtime-nd form); here the knee / foot rows of unused slots read the base row instead
 // and are never used.
-template <bool VEC, bool HOUND, int NDC = 0>
+// VAR: the gt_anymal_variant form (gymtask.h ABI 6; HoundTerrain, Hound_terrain.py:304-310, :347): v's links
+// terminate too, the knees terminate when it says so, and the base-height term has its target.  Only this form
+// reads v and the extra contact rows; with VAR false the function is what it was before the parameter existed.
+template <bool VEC, bool HOUND, int NDC = 0, bool VAR = false>
 __device__ __forceinline__ bool post_a_env(const gt_anymal_params& p, const gt_anymal_buffers& b,
-                                           const gt_anymal_hound& h, const int e) {
+                                           const gt_anymal_hound& h, const int e,
+                                           const gt_anymal_variant& v = gt_anymal_variant{}) {
 #pragma clang fp contract(off)
   static_assert(NDC == 0 || (VEC && !HOUND && NDC % 4 == 0 && NDC <= 16), "compile-time rows: AnymalTerrain, VEC");
+  static_assert(!(VAR && HOUND), "a variant and the UsefulHound extension exclude each other");
   const int nd = NDC > 0 ? NDC : p.num_dofs, nb = p.num_bodies;
   const int na = HOUND ? h.num_actions : nd;  // torques / actions width and dof_state row width
   const size_t N = p.num_envs;
@@ -139,6 +144,16 @@ __device__ __forceinline__ bool post_a_env(const gt_anymal_params& p, const gt_a
     for (int k = 0; k < 4; ++k)
 #pragma unroll
       for (int c = 0; c < 3; ++c) fsh[k][c] = k < h.num_shoulders ? cf[3 * h.shoulder_idx[k] + c] : 0.0f;
+  }
+  float fterm[4][3];
+  if constexpr (VAR) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (NDC > 0) fterm[k][c] = cf[3 * (k < v.num_term_links ? v.term_link_idx[k] : p.base_index) + c];
+        else fterm[k][c] = k < v.num_term_links ? cf[3 * v.term_link_idx[k] + c] : 0.0f;
+      }
   }
   float tq[kMaxActions], act[kMaxActions], lact[kMaxActions], lqd[16], dq[16], dqd[16];
   if constexpr (HOUND) {
@@ -209,6 +224,11 @@ __device__ __forceinline__ bool post_a_env(const gt_anymal_params& p, const gt_a
 #pragma unroll
     for (int k = 0; k < 4; ++k) sh_count += (k < h.num_shoulders && norm3(fsh[k]) > 1.0f) ? 1 : 0;
     if (knee_count > 0 || sh_count > 0) reset = true;
+  } else if constexpr (VAR) {
+    int term_count = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) term_count += (k < v.num_term_links && norm3(fterm[k]) > 1.0f) ? 1 : 0;
+    if (((v.knees_terminate || !p.allow_knee_contacts) && knee_count > 0) || term_count > 0) reset = true;
   } else {
     if (!p.allow_knee_contacts && knee_count > 0) reset = true;
   }
@@ -222,7 +242,7 @@ __device__ __forceinline__ bool post_a_env(const gt_anymal_params& p, const gt_a
   const float r_lin_z = sq(blv[2]) * p.s_lin_vel_z;
   const float r_ang_xy = (sq(bav[0]) + sq(bav[1])) * p.s_ang_vel_xy;
   const float r_orient = (sq(pg[0]) + sq(pg[1])) * p.s_orient;
-  const float r_height = sq(root[2] - 0.52f) * p.s_base_height;
+  const float r_height = sq(root[2] - (VAR ? v.base_height_target : 0.52f)) * p.s_base_height;
   float s_tq = 0.f, s_acc = 0.f, s_rate = 0.f;
 #pragma unroll
   for (int j = 0; j < kMaxActions; ++j) {

@@ -70,7 +70,15 @@ class GtAnymalBuffers(C.Structure):
         (n, C.c_void_p) for n in ("rew_buf", "episode_sums", "base_lin_vel", "base_ang_vel", "projected_gravity",
                                   "obs_buf", "noise_scale", "reset_count", "host_count")] + [
         ("seq", C.c_int32), ("reset_masks", C.c_void_p), ("obs_out", C.c_void_p), ("time_outs", C.c_void_p),
-        ("clip_obs", C.c_float), ("measured_heights", C.c_void_p), ("hound", C.c_void_p), ("obs_mirror", C.c_void_p)]
+        ("clip_obs", C.c_float), ("measured_heights", C.c_void_p), ("hound", C.c_void_p), ("obs_mirror", C.c_void_p),
+        ("variant", C.c_void_p)]
+
+
+class GtAnymalVariant(C.Structure):
+    """gt_anymal_variant (include/gymtask.h, ABI 6): AnymalTerrain's tail with extra terminating links, knees that
+    terminate whatever allowKneeContacts says, and its own base-height target (HoundTerrain)."""
+    _fields_ = [("base_height_target", C.c_float), ("knees_terminate", C.c_int32), ("num_term_links", C.c_int32),
+                ("term_link_idx", C.c_int32 * 4)]
 
 
 class GtAnymalHound(C.Structure):
@@ -494,6 +502,7 @@ class AnymalTailKernels:
         # (struct field, task attribute) of the buffers whose storage the kernels use
         self._stable = [(n, "last_hound_dof_vel" if (self.hound and n == "last_dof_vel") else n) for n in self._STABLE]
         self._h = self._hound_struct() if self.hound else None
+        self._v = self._variant_struct(getattr(t, "tail_variant", None))
 
     def _hound_struct(self):
         t = self.task
@@ -515,6 +524,23 @@ class AnymalTailKernels:
         h.arm_noise2 = float(t.houndarm_dof_noise * 2.0)  # useful_hound.py:598, a Python double cast once
         self._h_keep = (rb, t.arm_commands, t._pos_control, t._effort_control)
         return h
+
+    @staticmethod
+    def _variant_struct(variant):
+        """The task's tail_variant = (base height target, knees terminate, terminating link indices) as the C struct;
+        None for a task without one."""
+        if variant is None:
+            return None
+        target, knees, links = variant
+        if len(links) > 4:
+            raise ValueError(f"gt_anymal_variant holds at most 4 terminating links, the task names {len(links)}")
+        v = GtAnymalVariant()
+        v.base_height_target = float(target)
+        v.knees_terminate = int(bool(knees))
+        v.num_term_links = len(links)
+        for k, i in enumerate(links):
+            v.term_link_idx[k] = int(i)
+        return v
 
     def __del__(self):
         if getattr(self, "_host_words", None) and _lib is not None:
@@ -539,6 +565,7 @@ class AnymalTailKernels:
                 assert v.is_contiguous() and v.device.type == "cuda", attr
                 setattr(b, name, v.data_ptr())
             b.hound = C.cast(C.pointer(self._h), C.c_void_p) if self._h is not None else None
+            b.variant = C.cast(C.pointer(self._v), C.c_void_p) if self._v is not None else None
             b.reset_buf = self.reset_bool.data_ptr()
             b.episode_sums = self.sums.data_ptr()
             b.noise_scale = self.noise_scale.data_ptr()
@@ -583,7 +610,8 @@ class AnymalTailKernels:
             # off by default (GS_FUSED_TAIL=1 turns it on): measured no faster than the separate launch -- the
             # physics kernel grew by what post_a took (0.1106 -> 0.1185 ms, 30.0 vs 29.8 M env-steps/s,
             # profiles/r06i_fused_tail_ab.txt): the tail's cost is its own dependent chain, not the launch
-            ok = self._tail_ok = (os.environ.get("GS_FUSED_TAIL", "0") == "1" and not self.hound and self.nd % 4 == 0
+            ok = self._tail_ok = (os.environ.get("GS_FUSED_TAIL", "0") == "1" and not self.hound and self._v is None
+                                  and self.nd % 4 == 0
                                   and t.gym.amd_pd_tail_supported(t.sim))
         if not ok or not (t.torques.is_contiguous() and t.actions.is_contiguous()):
             return None

@@ -755,7 +755,8 @@ def load_raw(root: str, filename: str) -> RawModel:
     if os.path.isfile(path) and path.endswith(".xml"):
         from . import _mjcf
         return _mjcf.parse_mjcf(path)
-    key2 = "/".join(filename.replace(os.sep, "/").split("/")[-2:])
+    # (of the whole path: Hound_terrain.py:212-216 passes the directory as the root and "Hound.urdf" as the file)
+    key2 = "/".join(path.replace(os.sep, "/").split("/")[-2:])
     for key in (key2, base):
         if key in PACKED_INDEX:
             with open(os.path.join(PACKED_DIR, PACKED_INDEX[key])) as f:

@@ -2,11 +2,13 @@
 from .ant import Ant
 from .anymal_terrain import AnymalTerrain
 from .cartpole import Cartpole
+from .hound_terrain import HoundTerrain
 from .useful_hound import UsefulHound
 
 isaacgym_task_map = {
     "Ant": Ant,
     "AnymalTerrain": AnymalTerrain,
     "Cartpole": Cartpole,
+    "HoundTerrain": HoundTerrain,
     "UsefulHound": UsefulHound,
 }

@@ -50,6 +50,10 @@ REWARD_TERMS = ["lin_vel_xy", "lin_vel_z", "ang_vel_z", "ang_vel_xy", "orient", 
 
 class AnymalTerrain(VecTask):
     supports_fused_physics = True
+    # what a task built on this one (tasks/hound_terrain.py) changes without restating the methods below
+    actor_name = "anymal"
+    base_link_name = "base"
+    base_height_target = 0.52  # compute_reward's base-height term (anymal_terrain.py:331)
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture,
                  force_render):
@@ -216,8 +220,7 @@ class AnymalTerrain(VecTask):
         path = os.path.join(asset_root, self.cfg["env"]["urdfAsset"]["file"])
         return os.path.dirname(path), os.path.basename(path)
 
-    def _create_envs(self, num_envs, spacing, num_per_row):
-        asset_root, asset_file = self._asset_location()
+    def _asset_options(self):
         opts = gymapi.AssetOptions()
         opts.default_dof_drive_mode = gymapi.DOF_MODE_EFFORT
         opts.collapse_fixed_joints = True
@@ -230,7 +233,11 @@ class AnymalTerrain(VecTask):
         opts.armature = 0.0
         opts.thickness = 0.01
         opts.disable_gravity = False
-        asset = self.gym.load_asset(self.sim, asset_root, asset_file, opts)
+        return opts
+
+    def _create_envs(self, num_envs, spacing, num_per_row):
+        asset_root, asset_file = self._asset_location()
+        asset = self.gym.load_asset(self.sim, asset_root, asset_file, self._asset_options())
         self.num_dof = self.gym.get_asset_dof_count(asset)
         self.num_bodies = self.gym.get_asset_rigid_body_count(asset)
 
@@ -243,7 +250,7 @@ class AnymalTerrain(VecTask):
         start_pose = gymapi.Transform()
         start_pose.p = gymapi.Vec3(*self.base_init_state[:3])
 
-        body_names = self.gym.get_asset_rigid_body_names(asset)
+        body_names = self.body_names = self.gym.get_asset_rigid_body_names(asset)
         self.dof_names = self.gym.get_asset_dof_names(asset)
         foot = self.cfg["env"]["urdfAsset"]["footName"]
         knee = self.cfg["env"]["urdfAsset"]["kneeName"]
@@ -281,7 +288,7 @@ class AnymalTerrain(VecTask):
             for sp in shape_props:
                 sp.friction = friction_host[i % num_buckets]
             self.gym.set_asset_rigid_shape_properties(asset, shape_props)
-            handle = self.gym.create_actor(env_handle, asset, start_pose, "anymal", i, 0, 0)
+            handle = self.gym.create_actor(env_handle, asset, start_pose, self.actor_name, i, 0, 0)
             self.gym.set_actor_dof_properties(env_handle, handle, dof_props)
             self.envs.append(env_handle)
             self.anymal_handles.append(handle)
@@ -289,7 +296,8 @@ class AnymalTerrain(VecTask):
             self.feet_indices[i] = self.gym.find_actor_rigid_body_handle(self.envs[0], self.anymal_handles[0], n)
         for i, n in enumerate(knee_names):
             self.knee_indices[i] = self.gym.find_actor_rigid_body_handle(self.envs[0], self.anymal_handles[0], n)
-        self.base_index = self.gym.find_actor_rigid_body_handle(self.envs[0], self.anymal_handles[0], "base")
+        self.base_index = self.gym.find_actor_rigid_body_handle(self.envs[0], self.anymal_handles[0],
+                                                                  self.base_link_name)
 
     # ------------------------------------------------------------------ terms
     def check_termination(self):
@@ -323,7 +331,7 @@ class AnymalTerrain(VecTask):
         r["lin_vel_z"] = torch.square(self.base_lin_vel[:, 2]) * rs["lin_vel_z"]
         r["ang_vel_xy"] = torch.sum(torch.square(self.base_ang_vel[:, :2]), dim=1) * rs["ang_vel_xy"]
         r["orient"] = torch.sum(torch.square(self.projected_gravity[:, :2]), dim=1) * rs["orient"]
-        r["base_height"] = torch.square(self.root_states[:, 2] - 0.52) * rs["base_height"]
+        r["base_height"] = torch.square(self.root_states[:, 2] - self.base_height_target) * rs["base_height"]
         r["torques"] = torch.sum(torch.square(self.torques), dim=1) * rs["torque"]
         r["joint_acc"] = torch.sum(torch.square(self.last_dof_vel - self.dof_vel), dim=1) * rs["joint_acc"]
         knee_contact = torch.norm(self.contact_forces[:, self.knee_indices, :], dim=2) > 1.0
