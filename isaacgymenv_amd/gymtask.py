@@ -611,9 +611,19 @@ class AnymalTailKernels:
             # physics kernel grew by what post_a took (0.1106 -> 0.1185 ms, 30.0 vs 29.8 M env-steps/s,
             # profiles/r06i_fused_tail_ab.txt): the tail's cost is its own dependent chain, not the launch
             ok = self._tail_ok = (os.environ.get("GS_FUSED_TAIL", "0") == "1" and not self.hound and self._v is None
-                                  and self.nd % 4 == 0
-                                  and t.gym.amd_pd_tail_supported(t.sim))
-        if not ok or not (t.torques.is_contiguous() and t.actions.is_contiguous()):
+                                  and self.nd % 4 == 0)
+        if not ok:
+            return None
+        # the kernel form follows the drives and only the lane team has the tail: upload pending dof properties now
+        # (the launch would, after this choice), which refreshes kernel_variant; asked of a sim on the lane team, what
+        # else gs_sim_pd_tail_supported checks is fixed (no terrain mesh)
+        if t.sim.drives_dirty:
+            t.sim.apply_drives()
+        if t.sim.kernel_variant != 2:
+            return None
+        if self._tail_sim_ok is None:
+            self._tail_sim_ok = t.gym.amd_pd_tail_supported(t.sim)
+        if not self._tail_sim_ok or not (t.torques.is_contiguous() and t.actions.is_contiguous()):
             return None
         b = self._buffers()
         if any(x % 16 for x in (b.torques, b.actions, b.last_actions, b.last_dof_vel, b.dof_state)):
@@ -627,6 +637,7 @@ class AnymalTailKernels:
         self.task.reset_buf = self.reset_bool
 
     _tail_ok = None
+    _tail_sim_ok = None
     _ids_buf = None
 
     def post_ab_applies(self) -> bool:

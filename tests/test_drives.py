@@ -363,3 +363,41 @@ def test_anymal_drives_leave_the_lane_team_kernel():
                                            np.zeros((len(idx), 12)), drives, 1, bits))
     H.assert_close_or_explained(H.state_fields(g_root, g_dof), H.state_fields(o_root, o_dof), rerun,
                                 max_env_frac=5e-3, what="anymal drives gpu (one env per lane) vs oracle")
+
+
+@pytest.mark.gpu
+def test_refused_dof_property_table_leaves_the_sim_untouched(monkeypatch):
+    """kernel_variant 2 forced (GS_PHYSICS_KERNEL=team): the lane team reads no per-actor dof properties, so binding a
+    table with drive gains is refused -- before anything of it is in force.  17 envs (a full 16-env workgroup and a
+    tail env): the kernel form stays 2, and three fused PD steps end bit-identical to those of a sim that was never
+    asked."""
+    from isaacgymenv_amd.isaacgym import _lib
+    monkeypatch.setenv("GS_PHYSICS_KERNEL", "team")
+    n = 17
+    root, dof, _, mu = H.anymal_states(n, seed=6)
+    L = _lib.lib()
+    sims = []
+    for _ in range(2):
+        gym, sim = H.make_gpu_sim("anymal", n, H.ANYMAL_PARAMS)
+        assert L.gs_sim_kernel_variant(sim.handle) == 2
+        H.load_state_into(sim, root, dof, mu)
+        gym.refresh_dof_state_tensor(sim)
+        sims.append((gym, sim))
+    asked = sims[0][1]
+    table = torch.zeros((6, 12, n), dtype=torch.float32, device="cuda:0")  # [GS_DOFP_FIELDS][nd][N]
+    table[0], table[1], table[2] = 80.0, 2.0, 80.0  # drive stiffness and damping, effort; lower = upper: no limits
+    assert L.gs_sim_bind_dof_properties_env(asked.handle, table.data_ptr(), 1, 0) != 0
+    assert ("gs_sim_bind_dof_properties_env: the lane-team kernel (kernel_variant 2) has no joint drives or per-actor "
+            "dof properties") in L.gs_last_error().decode()
+    assert L.gs_sim_kernel_variant(asked.handle) == 2
+    acts = torch.from_numpy(np.random.RandomState(1).uniform(-1, 1, (3, n, 12)).astype(np.float32)).to("cuda:0")
+    default = torch.from_numpy(dof[:, :, 0].mean(0).astype(np.float32)).to("cuda:0")
+    out = []
+    for gym, sim in sims:
+        torques = torch.zeros((n, 12), device="cuda:0")
+        for a in acts:
+            gym.amd_pd_decimation_step(sim, a, default, 80.0, 2.0, 0.5, 80.0, 4, 1, torques)
+        torch.cuda.synchronize()
+        out.append((sim.state.clone(), torques, sim.contact_tensor.clone()))
+    for what, x, y in zip(("state", "torques", "contact forces"), *out):
+        assert torch.isfinite(x).all() and torch.equal(x, y), what

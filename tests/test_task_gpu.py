@@ -221,6 +221,39 @@ def test_fused_tail_in_physics_launch_is_bit_identical_to_post_a(terrain, monkey
     assert n_reset_steps >= 2
 
 
+def test_fused_tail_follows_the_kernel_form_across_drive_changes(monkeypatch):
+    """GS_FUSED_TAIL=1 and dof properties that change mid-run: a position drive on one actor moves the sim to the
+    one-env-per-lane kernel, which has no tail -- the steps go on with the separate post_a launch instead of handing
+    gs_sim_pd_step a tail it refuses -- and once the gains are zero again the lane team and its tail are back."""
+    from isaacgymenv_amd.isaacgym import gymapi
+    n = 256
+    monkeypatch.setenv("GS_FUSED_TAIL", "1")
+    env = _make("AnymalTerrain", n, monkeypatch)
+    assert env.push_interval > 16  # no push step (separate launch) inside the 9 steps below
+    gen = torch.Generator(device="cuda:0").manual_seed(5)
+    acts = [2 * torch.rand((n, 12), device="cuda:0", generator=gen) - 1 for _ in range(9)]
+
+    def steps(three):
+        n0 = env.fused_tail_steps
+        for a in three:
+            obs, _, _, _ = env.step(a)
+        assert torch.isfinite(obs["obs"]).all()
+        return env.fused_tail_steps - n0
+
+    assert env.gym.amd_kernel_variant(env.sim) == 2
+    assert steps(acts[0:3]) == 3
+    e, h = env.envs[7], env.anymal_handles[7]
+    props = env.gym.get_actor_dof_properties(e, h)
+    props["driveMode"][2], props["stiffness"][2], props["damping"][2] = gymapi.DOF_MODE_POS, 40.0, 1.0
+    env.gym.set_actor_dof_properties(e, h, props)
+    assert steps(acts[3:6]) == 0
+    assert env.gym.amd_kernel_variant(env.sim) == 1
+    props["stiffness"][2], props["damping"][2] = 0.0, 0.0
+    env.gym.set_actor_dof_properties(e, h, props)
+    assert steps(acts[6:9]) == 3
+    assert env.gym.amd_kernel_variant(env.sim) == 2
+
+
 def test_anymal_full_episode(monkeypatch):
     n = 512
     env = _make("AnymalTerrain", n, monkeypatch)

@@ -1,13 +1,15 @@
 """Dump a host-backend replay case for the ASan/UBSan driver (tools/asan/host_replay.cpp).
 
-    python tools/asan/dump_case.py <out.bin> [--case hound111|hound|anymal|ant] [--n N]
+    python tools/asan/dump_case.py <out.bin> [--case hound111|hound|anymal|anymal_trimesh|ant] [--n N]
 
 The case is the r04f UsefulHound failure by default: random Hound states (seed 13, spread
 0.5), actions RandomState(2), the fused 4 x PD + 1 step on the host backend.  Format (little endian): a
 magic, the gs_model_desc arrays in model_desc() order (each: int64 count, int32 kind 0 int32 / 1 float64, data),
 the scalar model fields, gs_sim_params, then N, nd, ns, self-collision, ground flag, the ground's frictions and
-restitution, the SoA state, shape frictions, actions, default pose and
-the PD gains.  The driver also writes its outputs next to it (<out.bin>.out) for compare().
+restitution, the SoA state, shape frictions, actions, default pose,
+the PD gains and the terrain mesh (vertex and triangle counts, 0 0 for none; float32 vertices, uint32 triangles, the
+translation, the friction).  anymal_trimesh is ANYmal over a small heightfield with a 0.3 m step, whose columns the
+slope correction moves: the terrain builder (gs_terrain_build.hip) and the host TERR path.  The driver also writes its outputs next to it (<out.bin>.out) for compare().
 """
 import argparse
 import os
@@ -23,6 +25,17 @@ from isaacgymenv_amd.isaacgym import _lib  # noqa: E402
 from tests import helpers as H  # noqa: E402
 
 MAGIC = 0x47534153  # "GSAS"
+KIND = {"hound111": "hound", "anymal_trimesh": "anymal"}  # tests/helpers.make_host_sim's robot of a case
+
+
+def terrain(name):
+    """The case's heightfield mesh (tests/helpers.terrain_from_heights) or None: 4 x 4 m of 0.1 m cells, +-1 cm
+    roughness, a 0.3 m step along x = 0.5 (slope 3 > the 0.5 threshold: its vertices are moved onto the lower row)."""
+    if name != "anymal_trimesh":
+        return None
+    hf = np.random.RandomState(8).randint(-2, 3, (41, 41)).astype(np.int16)
+    hf[25:] += 60
+    return H.terrain_from_heights(hf, hs=0.1, vs=0.005, slope_threshold=0.5, shift=(-2.0, -2.0, 0.0))
 
 
 def case(name, n):
@@ -32,9 +45,19 @@ def case(name, n):
         act = np.random.RandomState(2).uniform(-1.0, 1.0, (root.shape[0], 18))
         default = np.array([0.0, 0.7854, -1.5708] * 4 + [0.0] * 6)
         return flat, H.HOUND_PARAMS, root, dof, mu, act, default
-    if name == "anymal":
+    if name in ("anymal", "anymal_trimesh"):
         art, flat = H.anymal()
         root, dof, _, mu = H.anymal_states(n, seed=4)
+        ter = terrain(name)
+        if ter is not None:  # over the mesh, across the step, 5 cm above the vertices under each base
+            rng = np.random.RandomState(12)
+            root[:, 0:2] = rng.uniform(-1.2, 1.2, (n, 2))
+            v = ter["oracle"]["vertices"].reshape(-1, 3)
+            for i in range(n):
+                near = (np.abs(v[:, 0] - root[i, 0]) < 0.15) & (np.abs(v[:, 1] - root[i, 1]) < 0.15)
+                root[i, 2] += v[near, 2].mean() + 0.05
+            return flat, dict(H.ANYMAL_PARAMS, has_ground=0), root, dof, mu, \
+                np.random.RandomState(0).uniform(-1, 1, (n, 12)), np.array([H.ANYMAL_DEFAULT[d] for d in art.dof_names()])
         act = np.random.RandomState(0).uniform(-1, 1, (n, 12))
         default = np.array([H.ANYMAL_DEFAULT[d] for d in art.dof_names()])
         return flat, H.ANYMAL_PARAMS, root, dof, mu, act, default
@@ -49,7 +72,8 @@ def write(path, name, n):
     loaded asset's model, its gs_sim_params, self-collision flag and ground), then the case's state and actions."""
     flat, params, root, dof, mu, act, default = case(name, n)
     N, nd = root.shape[0], dof.shape[1]
-    gym, sim = H.make_host_sim({"hound111": "hound"}.get(name, name), N, params, threads=1)
+    ter = terrain(name)
+    gym, sim = H.make_host_sim(KIND.get(name, name), N, params, terrain=ter, threads=1)
     flat, p = sim.asset.flat, sim.cparams
     desc, keep = _lib.model_desc(flat)
     ns = int(flat["ns"])
@@ -79,6 +103,14 @@ def write(path, name, n):
         f.write(np.ascontiguousarray(act, np.float32).tobytes())
         f.write(np.ascontiguousarray(default, np.float32).tobytes())
         f.write(struct.pack("<4f", 80.0, 2.0, 0.5, 80.0))
+        if ter is None:
+            f.write(struct.pack("<2q", 0, 0))
+        else:
+            v, t = np.ascontiguousarray(ter["vertices"], np.float32), np.ascontiguousarray(ter["triangles"], np.uint32)
+            f.write(struct.pack("<2q", v.shape[0], t.shape[0]))
+            f.write(v.tobytes())
+            f.write(t.tobytes())
+            f.write(struct.pack("<4d", *ter["shift"], ter["friction"]))
     return N, nd
 
 
@@ -97,7 +129,7 @@ def compare(path, name, n):
     import torch
     flat, params, root, dof, mu, act, default = case(name, n)
     N, nd = root.shape[0], dof.shape[1]
-    gym, sim = H.make_host_sim({"hound111": "hound"}.get(name, name), N, params, threads=1)
+    gym, sim = H.make_host_sim(KIND.get(name, name), N, params, terrain=terrain(name), threads=1)
     H.load_state_into(sim, root, dof, mu)
     gym.refresh_dof_state_tensor(sim)
     torques = torch.empty((N, nd))

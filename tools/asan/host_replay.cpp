@@ -2,7 +2,8 @@
 // Reads a case written by tools/asan/dump_case.py, builds the sim through the public C ABI (include/gymsim.h) on
 // the host backend (device -1: no HIP call), runs the fused PD step (gs_sim_pd_step: 4 x PD + 1 simulates) and
 // writes the final SoA state and the torques to <case>.out.  Built by tools/asan/run.sh with the host-side
-// sanitizers on gs_host.hip / gs_capi.hip (the solver, narrowphase and kinematics headers they instantiate).
+// sanitizers on gs_host.hip / gs_capi.hip / gs_model_pack.hip / gs_terrain_build.hip (and the solver, narrowphase,
+// kinematics and terrain headers they instantiate).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -92,6 +93,16 @@ int main(int argc, char** argv) {
   rd(act.data(), act.size());
   rd(def.data(), def.size());
   rd(g.data(), 4);
+  int64_t mesh[2];  // vertices, triangles of the terrain mesh (0 0: none)
+  rd(mesh, 2);
+  std::vector<float> tverts((size_t)mesh[0] * 3);
+  std::vector<uint32_t> ttris((size_t)mesh[1] * 3);
+  double tshift[4] = {0, 0, 0, 1};  // translation, friction
+  if (mesh[0] > 0) {
+    rd(tverts.data(), tverts.size());
+    rd(ttris.data(), ttris.size());
+    rd(tshift, 4);
+  }
   fclose(g_in);
 
   gs_sim* sim = gs_sim_create(-1, &p);
@@ -99,6 +110,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "host_replay: gs_sim_create failed: %s\n", gs_last_error());
     return 3;
   }
+  if (mesh[0] > 0)  // (before the model, as gymapi's add_triangle_mesh comes before prepare_sim)
+    check(gs_sim_add_triangle_mesh(sim, tverts.data(), mesh[0], ttris.data(), mesh[1], tshift, tshift[3], tshift[3],
+                                   0.0),
+          "gs_sim_add_triangle_mesh");
   check(gs_sim_set_model(sim, &m), "gs_sim_set_model");
   check(gs_sim_set_self_collision(sim, self_collide), "gs_sim_set_self_collision");
   if (ground) check(gs_sim_add_ground(sim, gnd[0], gnd[1], gnd[2]), "gs_sim_add_ground");
