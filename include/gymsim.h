@@ -251,6 +251,23 @@ int gs_sim_bind_force_sensors(gs_sim *sim, float *sensor_soa);
 /* refresh_force_sensor_tensor: SoA -> [N*n][6] (ant.py:233-235) */
 int gs_sim_refresh_force_sensor(gs_sim *sim, float *out, void *stream);
 
+/* The DOF force tensor (gym.acquire_dof_force_tensor; additive entry points, no ABI bump).  For dof j of env e:
+ * the force the solver applied at that dof in the LAST SUBSTEP of the last simulate (or fused PD step), everything
+ * evaluated at the start of that substep.  It is the sum of
+ *   actuation: the actuation force (gs_sim_simulate's dof_force, the fused step's PD torque) clamped to the dof's
+ *              effort;
+ *   drive:     from the estimate f_est = kp (q* - q - h qd) + kd (qd* - qd).  A drive within the dof's effort is
+ *              implicit and gives f_est - (h kd + h^2 kp)(qd_end - qd): the drive at the velocity the substep ends
+ *              with.  A saturated drive gives clamp(f_est, +-effort).
+ * Joint-limit and contact impulses are not part of it.  Parity with PhysX's DOF force sensor is unpinned.
+ * gs_sim_bind_dof_force: caller-owned, sim-lifetime SoA buffer [nd][N], bound after gs_sim_prepare; NULL unbinds
+ * (an unbound sim pays nothing).  Every kernel form fills it: the one-env-per-lane, wave-assisted and
+ * runtime-sized kernels and the host backend in their last substep; after a lane-team launch (no drive gains there)
+ * one small kernel on the same stream writes the effort-clamped actuation force. */
+int gs_sim_bind_dof_force(gs_sim *sim, float *dof_force_soa);
+/* refresh_dof_force_tensor: SoA -> the reference layout [N*nd] */
+int gs_sim_refresh_dof_force(gs_sim *sim, float *out, void *stream);
+
 /* Joint drives (ABI 4): gym.set_actor_dof_properties with driveMode / stiffness / damping
  * (useful_hound.py:391-404 sets them; PhysX articulation joint drives).  Per dof of the asset:
  * mode 1 DOF_MODE_POS drives with stiffness kp and damping kd toward the position / velocity targets,

@@ -333,6 +333,66 @@ typedef struct gt_ant_reset_args {
 int gt_ant_reset_flagged(const gt_ant_params *p, const gt_ant_buffers *b, int k, const gt_ant_reset_args *r,
                          void *stream);
 
+/* ---- the flat-ground tasks Anymal and Hound (tasks/anymal.py), fused; additive entry points, no ABI bump.
+ *
+ * gt_flat_post_physics: compute_observations + compute_reward (anymal.py:241-276, 312-386) in one launch, one env per
+ * lane, after the reset and the four refreshes of post_physics_step.  Per env it writes
+ *   obs_buf [N][48]: base linear velocity * lin_vel_scale (3), base angular velocity * ang_vel_scale (3), both in the
+ *                    base frame; quat_rotate(base quat, gravity_vec) (3); commands * (lin, lin, ang scale) (3);
+ *                    (dof_pos - default_dof_pos) * dof_pos_scale (12); dof_vel * dof_vel_scale (12); actions (12)
+ *   rew_buf [N]:     max(0, exp(-|cmd_xy - v_xy|^2 / 0.25) rew_lin_vel_xy + exp(-(cmd_yaw - w_z)^2 / 0.25) rew_ang_vel_z
+ *                    + sum(torques^2) rew_torque)   (the scales already multiplied by dt; torques = the refreshed DOF
+ *                    force tensor)
+ *   reset_buf [N]:   int64, 1 on |contact_forces[base_index]| > 1, any |contact_forces[knee_idx[i]]| > 1, or
+ *                    progress_buf >= max_episode_length - 1; else 0
+ * and records the per-wave ballots of the done mask in reset_masks and publishes the done count {count, seq} to
+ * host_count (gt_host_alloc words), as gt_ant_post_physics does.  Links are indices into contact_forces
+ * [N][num_bodies][3], so one kernel serves both robots.
+ * root_states [N][13], dof_state [N*12][2], torques / actions / default_dof_pos [N][12], commands / gravity_vec
+ * [N][3], progress_buf int64 [N]. */
+typedef struct gt_flat_params {
+    int32_t num_envs, num_dofs, num_bodies, base_index, num_knees;
+    int32_t knee_idx[8];
+    int32_t max_episode_length;
+    float lin_vel_scale, ang_vel_scale, dof_pos_scale, dof_vel_scale;
+    float rew_lin_vel_xy, rew_ang_vel_z, rew_torque;
+} gt_flat_params;
+
+typedef struct gt_flat_buffers {
+    const float *root_states, *dof_state, *contact_forces, *torques, *actions, *commands, *default_dof_pos,
+                *gravity_vec;
+    float *obs_buf, *rew_buf;
+    int64_t *reset_buf;
+    const int64_t *progress_buf;
+    int32_t *reset_count;        /* [3] device, zero-initialised accumulator (re-armed by the kernel) */
+    int32_t *host_count;         /* [2] host-mapped {count, seq} or NULL */
+    int32_t seq;
+    uint64_t *reset_masks;       /* [ceil(N/64)] the done mask's per-wave ballots (gt_flat_reset_flagged) */
+} gt_flat_buffers;
+
+int gt_flat_post_physics(const gt_flat_params *p, const gt_flat_buffers *b, void *stream);
+
+/* reset_idx (anymal.py:278-304), fused, for the k envs the previous gt_flat_post_physics flagged (its reset_masks
+ * ballots; env ids ascending = torch's nonzero order).  The five torch_rand_float draws, in the reference's order,
+ * are evaluated in-kernel from five consecutive torch.rand plans (sizes k*12, k*12, k, k, k), bit-identically to
+ * torch's Philox, each as range * u + lower:
+ *   dof_pos[e] = default_dof_pos[e] * U(0.5, 1.5), dof_vel[e] = U(-0.1, 0.1)
+ *   commands[e] = (U(x range), U(y range), U(yaw range))
+ *   progress_buf[e] = 0, reset_buf[e] = 1 (the reference's value), env_ids_out[rank] = e
+ * The caller then applies the reference's two indexed state sets with env_ids_out (one launch:
+ * amd_set_root_and_dof_state_indexed). */
+typedef struct gt_flat_reset_args {
+    gt_torch_rand_plan plan[5];        /* dof factors, dof velocities, command x, y, yaw */
+    float range[5], lower[5];
+    float *dof_state;                  /* [N*12][2] the task's dof tensor */
+    float *commands;                   /* [N][3] */
+    int64_t *progress_buf;             /* [N] */
+    int32_t *env_ids_out;              /* [>= k] */
+} gt_flat_reset_args;
+
+int gt_flat_reset_flagged(const gt_flat_params *p, const gt_flat_buffers *b, int k, const gt_flat_reset_args *r,
+                          void *stream);
+
 /* out[plan.numel] = torch.rand(plan.numel) for the given plan (checks torch_philox.h against torch) */
 int gt_torch_rand(const gt_torch_rand_plan *plan, float *out, void *stream);
 

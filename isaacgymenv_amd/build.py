@@ -20,7 +20,7 @@ ARCH = os.environ.get("GS_OFFLOAD_ARCH", "gfx950")
 LIBS = {
     "libgymsim.so": ["gs_physics.hip", "gs_phys_inst.hip", "gs_team.hip", "gs_kinematics.hip", "gs_host.hip",
                      "gs_generic.hip", "gs_model_pack.hip", "gs_terrain_build.hip", "gs_capi.hip"],
-    "libgymtask.so": ["gt_anymal.hip", "gt_hound.hip", "gt_ant.hip"],
+    "libgymtask.so": ["gt_anymal.hip", "gt_hound.hip", "gt_ant.hip", "gt_anymal_flat.hip"],
     "libgymrl.so": ["rl_gae.hip", "rl_grad.hip", "rl_rollout.hip", "rl_ppo_loss.hip", "rl_rms.hip", "rl_adam.hip", "rl_linear.hip",
                    "rl_policy.hip", "rl_infer.hip"],
 }
@@ -37,9 +37,10 @@ HEADERS = ["gs_internal.h", "gs_topologies.h", "gs_math.h", "gs_terrain.h", "gs_
            "gs_physics_impl.h", "torch_philox.h", "gt_anymal_tail.h", "gs_kernel_choice.h", "gs_model_pack.h",
            "gs_terrain_build.h"]
 # gs_phys_inst.hip is compiled once per (topology, kernel form): 0 simulate plane, 1 simulate terrain-mesh,
-# 2 fused PD step plane, 3 fused PD step terrain-mesh (gs_physics_impl.h)
+# 2 fused PD step plane, 3 fused PD step terrain-mesh (gs_physics_impl.h); 4-7 the same four with the DOF force
+# store compiled in (launched only while a sim has the tensor bound)
 INST_SRC = "gs_phys_inst.hip"
-INST_FORMS = (0, 1, 2, 3)
+INST_FORMS = (0, 1, 2, 3, 4, 5, 6, 7)
 
 
 def topologies() -> list:

@@ -50,6 +50,28 @@ const TopoEntry* find_topology(const gs_model_desc* m) {
     if (sig == g_topologies[i].sig) return &g_topologies[i];
   return nullptr;
 }
+
+// The DOF force tensor after a lane-team launch (DevParams::dof_force): the team runs only sims
+// with no drive gains and no per-actor table, so the tensor is the actuation force clamped to the asset's effort,
+// as the team's own substep clamps it.  src [N][nd] or null (= 0) -> out [nd][N]; consecutive threads are
+// consecutive envs, so the stores are full rows.
+__global__ void k_team_dof_force(const float* __restrict__ src, const float* __restrict__ effort, int N, int nd,
+                                 float* __restrict__ out) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)N * nd) return;
+  const int j = (int)(t / N), e = (int)(t - (long)j * N);
+  float f = src ? src[(size_t)e * nd + j] : 0.f;
+  const float ef = effort[j];
+  if (ef > 0.f) f = fminf(fmaxf(f, -ef), ef);
+  out[t] = f;
+}
+// refresh_dof_force_tensor: [nd][N] -> [N*nd]
+__global__ void k_refresh_dof_force(const float* __restrict__ soa, int N, int nd, float* __restrict__ out) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)N * nd) return;
+  const int e = (int)(t / nd), j = (int)(t - (long)e * nd);
+  out[t] = soa[(size_t)j * N + e];
+}
 }  // namespace
 
 struct gs_sim {
@@ -383,6 +405,17 @@ double ms_since(host_clock::time_point t0) {
 }
 }  // namespace
 
+// The lane-team kernels do not write the DOF force tensor: with one bound, their launch is followed on its stream by
+// k_team_dof_force over the actuation force the launch applied last (tau: [N][nd] or null)
+static hipError_t team_dof_force(gs_sim* s, const float* tau, hipStream_t st) {
+  if (s->variant != 2 || !s->dp.dof_force) return hipSuccess;
+  const long n = (long)s->N * s->nd;
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_team_dof_force, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tau, &s->d_model->effort[0],
+                     s->N, s->nd, s->dp.dof_force);
+  return hipGetLastError();
+}
+
 int gs_sim_simulate(gs_sim* s, const float* dof_force, void* stream) {
   if (ready(s, "gs_sim_simulate")) return -1;
   if (s->host) {
@@ -394,6 +427,7 @@ int gs_sim_simulate(gs_sim* s, const float* dof_force, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   timing_begin(s, st);
   hipError_t e = s->sim_fn(s->d_model, s->dp, buffers(s), dof_force, st);
+  if (e == hipSuccess) e = team_dof_force(s, dof_force, st);
   timing_end(s, st);
   return e == hipSuccess ? 0 : hip_fail(e, "gs_sim_simulate");
 }
@@ -455,6 +489,7 @@ int gs_sim_pd_step(gs_sim* s, const gs_pd_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   timing_begin(s, st);
   hipError_t e = s->pd_fn(s->d_model, s->dp, buffers(s), d, st);
+  if (e == hipSuccess) e = team_dof_force(s, a->torques_out, st);
   timing_end(s, st);
   return e == hipSuccess ? 0 : hip_fail(e, "gs_sim_pd_step");
 }
@@ -650,6 +685,28 @@ int gs_sim_refresh_force_sensor(gs_sim* s, float* out, void* stream) {
   }
   hipError_t e = launch_refresh_sensor(s->sens, s->N, s->h_model.nsens, out, (hipStream_t)stream);
   return e == hipSuccess ? 0 : hip_fail(e, "gs_sim_refresh_force_sensor");
+}
+
+int gs_sim_bind_dof_force(gs_sim* s, float* soa) {
+  if (ready(s, "gs_sim_bind_dof_force")) return -1;
+  s->dp.dof_force = soa;
+  return 0;
+}
+
+int gs_sim_refresh_dof_force(gs_sim* s, float* out, void* stream) {
+  if (ready(s, "gs_sim_refresh_dof_force")) return -1;
+  if (!s->dp.dof_force) return fail("gs_sim_refresh_dof_force: no buffer bound (gs_sim_bind_dof_force)");
+  if (!out) return fail("gs_sim_refresh_dof_force: bad buffers");
+  if (s->host) {
+    host_soa_to_aos(s->dp.dof_force, s->N, s->nd, 1, out, s->pool);
+    return 0;
+  }
+  const long n = (long)s->N * s->nd;
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_refresh_dof_force, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     s->dp.dof_force, s->N, s->nd, out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : hip_fail(e, "gs_sim_refresh_dof_force");
 }
 
 int gs_debug_terrain_query(gs_sim* s, const float* centres, const float* radii, int n, float* out, void* stream) {

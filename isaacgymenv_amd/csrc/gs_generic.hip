@@ -258,7 +258,7 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
                                 const float* __restrict__ mu, int N, int e, const float* __restrict__ tau_e,
                                 float* __restrict__ ws, float* __restrict__ cf, float* __restrict__ sens, GBody& B,
                                 float* Ml, float* rowf, int* rowi, float* vec,
-                                std::conditional_t<FEAT, GFeat, GNoFeat>& X) {
+                                std::conditional_t<FEAT, GFeat, GNoFeat>& X, float* __restrict__ dff) {
   const int lane = threadIdx.x & (kGW - 1);
   const int nb = L->nb, nd = L->nd, fb = L->fixed_base;
   const int nbase = fb ? 0 : 6, nv = nbase + nd;
@@ -406,6 +406,13 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
     rhs[nbase + j] = r;
     dforce[j] = df;
     dimpl[j] = imp;
+    // the DOF force tensor (gs_solver.h substep's dff_soa): actuation + drive estimate, and the qd half of an
+    // implicit drive's -(h kd + h^2 kp)(qd_end - qd); the store after the integration completes it
+    if (dff) {
+      float f = t + df;
+      if (imp != 0.f) f += h * (gdofp(P, nd, e, 1, j, M->dkd[j]) + h * gdofp(P, nd, e, 0, j, M->dkp[j])) * qd[j];
+      dff[(size_t)j * N + e] = f;
+    }
   }
   // ---------------- CRBA (lane = body): row of body i's dof, and its base block (entries of dofs on no common
   // path stay zero)
@@ -776,6 +783,8 @@ __device__ void generic_substep(const DevModel* __restrict__ M, const DevLinks* 
   for (int j = lane; j < nd; j += kGW) {
     st[(size_t)(13 + j) * N + e] = q[j];
     st[(size_t)(13 + nd + j) * N + e] = qd[j];
+    if (dff && P.any_drive && dimpl[j] != 0.f)  // (the lane that stored dof j's first half)
+      dff[(size_t)j * N + e] -= h * (gdofp(P, nd, e, 1, j, M->dkd[j]) + h * gdofp(P, nd, e, 0, j, M->dkp[j])) * qd[j];
   }
   // net contact force per reported link, sum of lambda / h over the contact's rows in its frame (plane: z, x, y)
   if (cf) {
@@ -828,7 +837,8 @@ __global__ __launch_bounds__(kGW) void k_simulate_generic(const DevModel* __rest
   for (int s = 0; s < P.substeps; ++s) {
     const bool last = s == P.substeps - 1;
     generic_substep<FEAT>(M, L, G, P, Bf.state, Bf.mu, Bf.N, e, tau ? tau + (size_t)e * L->nd : nullptr, ws,
-                          (last && P.collect) ? Bf.cf : nullptr, last ? Bf.sens : nullptr, B, Ml, rowf, rowi, vec, X);
+                          (last && P.collect) ? Bf.cf : nullptr, last ? Bf.sens : nullptr, B, Ml, rowf, rowi, vec, X,
+                          last ? P.dof_force : nullptr);
   }
 }
 

@@ -116,8 +116,8 @@ void simulate_env_qs(const DevModel* M, const DevParams& P, const SimBuffers& B,
       qout[5 * c + 2] = n[0]; qout[5 * c + 3] = n[1]; qout[5 * c + 4] = n[2];
     }
     const bool last = (sstep == P.substeps - 1) && P.collect;
-    substep<T, true, 1, 1, true>(M, P, s, tau, B.mu, N, e, lds, B.cf, last, sstep == P.substeps - 1 ? B.sens : nullptr,
-                                 qout);
+    substep<T, true, 1, 1, true, 0, true>(M, P, s, tau, B.mu, N, e, lds, B.cf, last, sstep == P.substeps - 1 ? B.sens : nullptr,
+                                 qout, nullptr, sstep == P.substeps - 1 ? P.dof_force : nullptr);
   }
   store_state<T>(B.state, N, e, s);
 }
@@ -132,12 +132,12 @@ void host_sim(const DevModel* M, const DevParams& P, const SimBuffers& B, const 
   } else if (P.has_terrain) {
     pool->run(B.N, [&](int b, int e1) {
       float* lds = scratch(LaneCfg<T, true>::SLOTS);
-      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, true>::SLOTS); simulate_env<T, true, 1>(M, P, B, tau, e, lds); }
+      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, true>::SLOTS); simulate_env<T, true, 1, true, false, true>(M, P, B, tau, e, lds); }
     });
   } else {
     pool->run(B.N, [&](int b, int e1) {
       float* lds = scratch(LaneCfg<T, false>::SLOTS);
-      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, false>::SLOTS); simulate_env<T, false, 1>(M, P, B, tau, e, lds); }
+      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, false>::SLOTS); simulate_env<T, false, 1, true, false, true>(M, P, B, tau, e, lds); }
     });
   }
 }
@@ -147,12 +147,12 @@ void host_pd(const DevModel* M, const DevParams& P, const SimBuffers& B, const P
   if (P.has_terrain) {
     pool->run(B.N, [&](int b, int e1) {
       float* lds = scratch(LaneCfg<T, true>::SLOTS);
-      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, true>::SLOTS); pd_step_env<T, true, 1>(M, P, B, A, e, lds); }
+      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, true>::SLOTS); pd_step_env<T, true, 1, true, true>(M, P, B, A, e, lds); }
     });
   } else {
     pool->run(B.N, [&](int b, int e1) {
       float* lds = scratch(LaneCfg<T, false>::SLOTS);
-      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, false>::SLOTS); pd_step_env<T, false, 1>(M, P, B, A, e, lds); }
+      for (int e = b; e < e1; ++e) { poison(lds, LaneCfg<T, false>::SLOTS); pd_step_env<T, false, 1, true, true>(M, P, B, A, e, lds); }
     });
   }
 }

@@ -104,6 +104,10 @@ struct DevParams {
   // resident sweeps of the row-lane form, 0 / 1 (GS_TEAM_RESIDENT_SWEEPS at gs_sim_create); -1 = the kernel's own
   // default (gs_team.hip team_resident_sweeps)
   int team_resident;
+  // the DOF force tensor (gs_sim_bind_dof_force): [nd][N], written in a launch's last substep by the
+  // kernels that compile gs_solver.h's substep and by the runtime-sized kernel; null = not bound.  (The lane-team
+  // kernels do not read it: gs_capi.hip follows their launch with k_team_dof_force.)
+  float* dof_force;
 };
 #define GS_DOFP_FIELDS 6
 

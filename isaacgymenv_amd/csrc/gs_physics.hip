@@ -159,13 +159,13 @@ hipError_t launch_set_dof(float* state, int N, int nd, const float* src, const i
 }
 
 // per-form launchers: defined in gs_physics_impl.h, instantiated in gs_phys_inst.hip
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_sim_plane(const DevModel*, const DevParams&, const SimBuffers&, const float*, hipStream_t);
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_sim_terr(const DevModel*, const DevParams&, const SimBuffers&, const float*, hipStream_t);
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_pd_plane(const DevModel*, const DevParams&, const SimBuffers&, const PdDev&, hipStream_t);
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_pd_terr(const DevModel*, const DevParams&, const SimBuffers&, const PdDev&, hipStream_t);
 
 template <class T>
@@ -173,11 +173,14 @@ hipError_t launch_dbg_pool(const DevModel*, const DevParams&, const SimBuffers&,
 
 template <class T>
 hipError_t launch_sim(const DevModel* M, const DevParams& P, const SimBuffers& B, const float* tau, hipStream_t st) {
-  return P.has_terrain ? launch_sim_terr<T>(M, P, B, tau, st) : launch_sim_plane<T>(M, P, B, tau, st);
+  // (DFF: the instantiation with the DOF force store, only while a buffer is bound)
+  if (P.dof_force) return P.has_terrain ? launch_sim_terr<T, true>(M, P, B, tau, st) : launch_sim_plane<T, true>(M, P, B, tau, st);
+  return P.has_terrain ? launch_sim_terr<T, false>(M, P, B, tau, st) : launch_sim_plane<T, false>(M, P, B, tau, st);
 }
 template <class T>
 hipError_t launch_pd(const DevModel* M, const DevParams& P, const SimBuffers& B, const PdDev& A, hipStream_t st) {
-  return P.has_terrain ? launch_pd_terr<T>(M, P, B, A, st) : launch_pd_plane<T>(M, P, B, A, st);
+  if (P.dof_force) return P.has_terrain ? launch_pd_terr<T, true>(M, P, B, A, st) : launch_pd_plane<T, true>(M, P, B, A, st);
+  return P.has_terrain ? launch_pd_terr<T, false>(M, P, B, A, st) : launch_pd_plane<T, false>(M, P, B, A, st);
 }
 
 #define GS_TOPO_ENTRY(T, SIG)                                                                          \

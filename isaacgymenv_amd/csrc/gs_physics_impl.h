@@ -8,7 +8,7 @@
 namespace gs_phys {
 
 // ---------------------------------------------------------------- kernels
-template <class T, bool TERR, bool SELF>
+template <class T, bool TERR, bool SELF, bool DFF>
 __global__ __launch_bounds__((LaneCfg<T, TERR>::LB), 1) void k_simulate(const DevModel* __restrict__ M, DevParams P,
                                                                 SimBuffers B, const float* __restrict__ tau_aos) {
   using C = LaneCfg<T, TERR>;
@@ -17,10 +17,10 @@ __global__ __launch_bounds__((LaneCfg<T, TERR>::LB), 1) void k_simulate(const De
   const int e = blockIdx.x * LB + threadIdx.x;
   if (e >= B.N) return;
   float* rows = C::GLOBAL ? B.rows + (size_t)blockIdx.x * C::SLOTS * LB + threadIdx.x : lds + threadIdx.x;
-  simulate_env<T, TERR, LB, SELF, SELF && C::SPLIT>(M, P, B, tau_aos, e, rows);
+  simulate_env<T, TERR, LB, SELF, SELF && C::SPLIT, DFF>(M, P, B, tau_aos, e, rows);
 }
 
-template <class T, bool TERR, bool SELF>
+template <class T, bool TERR, bool SELF, bool DFF>
 __global__ __launch_bounds__((LaneCfg<T, TERR>::LB), 1) void k_pd_step(const DevModel* __restrict__ M, DevParams P,
                                                                SimBuffers B, PdDev A) {
   using C = LaneCfg<T, TERR>;
@@ -29,7 +29,7 @@ __global__ __launch_bounds__((LaneCfg<T, TERR>::LB), 1) void k_pd_step(const Dev
   const int e = blockIdx.x * LB + threadIdx.x;
   if (e >= B.N) return;
   float* rows = C::GLOBAL ? B.rows + (size_t)blockIdx.x * C::SLOTS * LB + threadIdx.x : lds + threadIdx.x;
-  pd_step_env<T, TERR, LB, SELF>(M, P, B, A, e, rows);
+  pd_step_env<T, TERR, LB, SELF, DFF>(M, P, B, A, e, rows);
 }
 
 // ---------------------------------------------------------------- wave-assisted kernels (TERR, SELF)
@@ -205,7 +205,7 @@ __device__ __forceinline__ void wave_prepass(const DevModel* __restrict__ M, con
   GS_WPROF(3)
 }
 
-template <class T, bool TERR, bool SELF>
+template <class T, bool TERR, bool SELF, bool DFF>
 __global__ __launch_bounds__(kTerrWave, 1) void k_simulate_wave(const DevModel* __restrict__ M, DevParams P,
                                                                 SimBuffers B, const float* __restrict__ tau_aos) {
   using W = WaveCfg<T, TERR, SELF>;
@@ -226,9 +226,10 @@ __global__ __launch_bounds__(kTerrWave, 1) void k_simulate_wave(const DevModel* 
     wave_prepass<T, TERR, SELF>(M, P, B, e0, env_lane, s, lds, qin, qout GS_WPROF_ARGS);
     if (env_lane) {
       const bool last = (sstep == P.substeps - 1) && P.collect;
-      substep<T, TERR, LB, TERR ? LB : 0, SELF, W::PAIRS ? LB : 0>(
+      substep<T, TERR, LB, TERR ? LB : 0, SELF, W::PAIRS ? LB : 0, DFF>(
           M, P, s, tau, B.mu, N, e, lds + threadIdx.x, B.cf, last, sstep == P.substeps - 1 ? B.sens : nullptr,
-          qout + threadIdx.x, lds + threadIdx.x + NearRec<T>::SHW * LB);
+          qout + threadIdx.x, lds + threadIdx.x + NearRec<T>::SHW * LB,
+          sstep == P.substeps - 1 ? P.dof_force : nullptr);
     }
     GS_WPROF(4)
   }
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(kTerrWave, 1) void k_simulate_wave(const DevModel* 
   if (env_lane) store_state<T>(B.state, N, e, s);
 }
 
-template <class T, bool TERR, bool SELF>
+template <class T, bool TERR, bool SELF, bool DFF>
 __global__ __launch_bounds__(kTerrWave, 1) void k_pd_step_wave(const DevModel* __restrict__ M, DevParams P,
                                                                SimBuffers B, PdDev A) {
   using W = WaveCfg<T, TERR, SELF>;
@@ -257,9 +258,9 @@ __global__ __launch_bounds__(kTerrWave, 1) void k_pd_step_wave(const DevModel* _
     wave_prepass<T, TERR, SELF>(M, P, B, e0, env_lane, s, lds, qin, qout GS_WPROF_ARGS);
     if (env_lane) {
       const bool last = ((it % sub) == sub - 1) && P.collect;
-      substep<T, TERR, LB, TERR ? LB : 0, SELF, W::PAIRS ? LB : 0>(
+      substep<T, TERR, LB, TERR ? LB : 0, SELF, W::PAIRS ? LB : 0, DFF>(
           M, P, s, tau, B.mu, N, e, lds + threadIdx.x, B.cf, last, it == total - 1 ? B.sens : nullptr,
-          qout + threadIdx.x, lds + threadIdx.x + NearRec<T>::SHW * LB);
+          qout + threadIdx.x, lds + threadIdx.x + NearRec<T>::SHW * LB, it == total - 1 ? P.dof_force : nullptr);
       if (it == n_pd - 1) pd_dof_out<T>(A, e, s);
     }
     GS_WPROF(4)
@@ -270,7 +271,8 @@ __global__ __launch_bounds__(kTerrWave, 1) void k_pd_step_wave(const DevModel* _
 
 }  // namespace gs_phys
 
-// launchers, one per kernel form (instantiated per topology in gs_phys_inst.hip).  Mesh sims run the
+// launchers, one per kernel form and DFF (the DOF force store compiled in, gs_solver.h substep: launched when a
+// buffer is bound, DevParams::dof_force), instantiated per topology in gs_phys_inst.hip.  Mesh sims run the
 // wave-assisted kernels.  Plane sims with self-collision whose envs are LDS-starved (<= 4 env lanes per
 // workgroup: UsefulHound): the simulate takes the split form when LaneCfg::SPLIT (k_pair_records, then
 // k_simulate reading the records; r03: 1.64 vs 2.05 ms per substep for the wave form), and the fused PD step
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(kTerrWave, 1) void k_pd_step_wave(const DevModel* _
 template <class T>
 constexpr bool kWavePlaneSelf = GS_WAVE_PLANE_SELF && T::NPK > 0 && LaneCfg<T, false>::LB <= 4 && !LaneCfg<T, false>::GLOBAL;
 
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_sim_plane(const DevModel* M, const DevParams& P, const SimBuffers& B, const float* tau, hipStream_t st) {
   constexpr int LB = LaneCfg<T, false>::LB;
   const dim3 grid((B.N + LB - 1) / LB);
@@ -296,15 +298,15 @@ hipError_t launch_sim_plane(const DevModel* M, const DevParams& P, const SimBuff
       for (int ss = 0; ss < P.substeps; ++ss) {
         P1.collect = P.collect && ss == P.substeps - 1;
         hipLaunchKernelGGL((gs_phys::k_pair_records<T>), pgrid, dim3(gs_phys::kTerrWave), 0, st, M, P1, B);
-        hipLaunchKernelGGL((gs_phys::k_simulate<T, false, true>), grid, dim3(LB), 0, st, M, P1, B, tau);
+        hipLaunchKernelGGL((gs_phys::k_simulate<T, false, true, DFF>), grid, dim3(LB), 0, st, M, P1, B, tau);
       }
     } else if constexpr (kWavePlaneSelf<T>) {
-      hipLaunchKernelGGL((gs_phys::k_simulate_wave<T, false, true>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, tau);
+      hipLaunchKernelGGL((gs_phys::k_simulate_wave<T, false, true, DFF>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, tau);
     } else {
-      hipLaunchKernelGGL((gs_phys::k_simulate<T, false, true>), grid, dim3(LB), 0, st, M, P, B, tau);
+      hipLaunchKernelGGL((gs_phys::k_simulate<T, false, true, DFF>), grid, dim3(LB), 0, st, M, P, B, tau);
     }
   } else {
-    hipLaunchKernelGGL((gs_phys::k_simulate<T, false, false>), grid, dim3(LB), 0, st, M, P, B, tau);
+    hipLaunchKernelGGL((gs_phys::k_simulate<T, false, false, DFF>), grid, dim3(LB), 0, st, M, P, B, tau);
   }
   return hipGetLastError();
 }
@@ -372,37 +374,37 @@ hipError_t launch_dbg_pool(const DevModel* M, const DevParams& P, const SimBuffe
   return e != hipSuccess ? e : e2;
 }
 
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_sim_terr(const DevModel* M, const DevParams& P, const SimBuffers& B, const float* tau, hipStream_t st) {
   constexpr int LB = LaneCfg<T, true>::LB;
   const dim3 grid((B.N + LB - 1) / LB);
   if (P.self_collide)
-    hipLaunchKernelGGL((gs_phys::k_simulate_wave<T, true, true>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, tau);
+    hipLaunchKernelGGL((gs_phys::k_simulate_wave<T, true, true, DFF>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, tau);
   else
-    hipLaunchKernelGGL((gs_phys::k_simulate_wave<T, true, false>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, tau);
+    hipLaunchKernelGGL((gs_phys::k_simulate_wave<T, true, false, DFF>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, tau);
   return hipGetLastError();
 }
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_pd_plane(const DevModel* M, const DevParams& P, const SimBuffers& B, const PdDev& A, hipStream_t st) {
   constexpr int LB = LaneCfg<T, false>::LB;
   const dim3 grid((B.N + LB - 1) / LB);
   if (P.self_collide) {
     if constexpr (kWavePlaneSelf<T>)
-      hipLaunchKernelGGL((gs_phys::k_pd_step_wave<T, false, true>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, A);
+      hipLaunchKernelGGL((gs_phys::k_pd_step_wave<T, false, true, DFF>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, A);
     else
-      hipLaunchKernelGGL((gs_phys::k_pd_step<T, false, true>), grid, dim3(LB), 0, st, M, P, B, A);
+      hipLaunchKernelGGL((gs_phys::k_pd_step<T, false, true, DFF>), grid, dim3(LB), 0, st, M, P, B, A);
   } else {
-    hipLaunchKernelGGL((gs_phys::k_pd_step<T, false, false>), grid, dim3(LB), 0, st, M, P, B, A);
+    hipLaunchKernelGGL((gs_phys::k_pd_step<T, false, false, DFF>), grid, dim3(LB), 0, st, M, P, B, A);
   }
   return hipGetLastError();
 }
-template <class T>
+template <class T, bool DFF>
 hipError_t launch_pd_terr(const DevModel* M, const DevParams& P, const SimBuffers& B, const PdDev& A, hipStream_t st) {
   constexpr int LB = LaneCfg<T, true>::LB;
   const dim3 grid((B.N + LB - 1) / LB);
   if (P.self_collide)
-    hipLaunchKernelGGL((gs_phys::k_pd_step_wave<T, true, true>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, A);
+    hipLaunchKernelGGL((gs_phys::k_pd_step_wave<T, true, true, DFF>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, A);
   else
-    hipLaunchKernelGGL((gs_phys::k_pd_step_wave<T, true, false>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, A);
+    hipLaunchKernelGGL((gs_phys::k_pd_step_wave<T, true, false, DFF>), grid, dim3(gs_phys::kTerrWave), 0, st, M, P, B, A);
   return hipGetLastError();
 }

@@ -270,11 +270,16 @@ GS_HD int pool_from_records(const DevModel* __restrict__ M, const float* __restr
 // PR > 0 (wave-assisted kernels): the self-collision narrowphase of this substep was already run by the whole
 // workgroup (pair_records, gs_physics_impl.h) on the shape world data shape_world wrote, and `prec` holds this
 // env's pair records at stride PR (pair_records' layout); the prepass only gathers them into the pool.
-template <class T, bool TERR, int LB = LaneCfg<T, TERR>::LB, int QS = 0, bool SELF = true, int PR = 0>
+// dff_soa (a launch's last substep, DevParams::dof_force bound): the DOF force tensor [nd][N] -- the
+// effort-clamped actuation force plus the drive's force, an implicit drive's at the velocity this substep ends with.
+// DFF = false compiles the store out: as a runtime branch alone it cost the one-env-per-lane kernels 90-700 bytes of
+// scratch per lane with nothing bound, so the launchers pick the instantiation (gs_physics_impl.h).
+template <class T, bool TERR, int LB = LaneCfg<T, TERR>::LB, int QS = 0, bool SELF = true, int PR = 0, bool DFF = false>
 GS_HD void substep(const DevModel* __restrict__ Min, const DevParams& P, EnvState<T>& s,
                                         const float* tau, const float* __restrict__ mu_g, int N, int e, float* lds,
                                         float* __restrict__ cf_soa, bool collect, float* __restrict__ sens_soa,
-                   const float* __restrict__ qres = nullptr, const float* __restrict__ prec = nullptr) {
+                   const float* __restrict__ qres = nullptr, const float* __restrict__ prec = nullptr,
+                   float* __restrict__ dff_soa = nullptr) {
   constexpr int NB = T::NB, NV = T::NV, NB6 = T::NBASE, NC = T::NC, ND = T::ND;
   constexpr int MS = T::MAXDEP + 1;
   // Keep the model pointer opaque per substep: the constants are re-read with
@@ -328,6 +333,15 @@ GS_HD void substep(const DevModel* __restrict__ Min, const DevParams& P, EnvStat
       const float ef = dofp(2, j, M->effort[j]);
       dimpl[j] = !(ef > 0.f) || fabsf(f) <= ef;
       dforce[j] = dimpl[j] ? f : clampf(f, -ef, ef);
+    }
+  }
+  // the DOF force store keeps the implicit dofs as one word of bits (dimpl[] itself dies after the mass matrix)
+  static_assert(ND <= 32, "implicit-drive bits are one 32-bit word");
+  unsigned dimplb = 0u;
+  if constexpr (DFF) {
+    if (dff_soa && P.any_drive) {
+#pragma unroll
+      for (int j = 0; j < ND; ++j) dimplb |= dimpl[j] ? (1u << j) : 0u;
     }
   }
 
@@ -694,6 +708,16 @@ GS_HD void substep(const DevModel* __restrict__ Min, const DevParams& P, EnvStat
       if (ef > 0.f) t = clampf(t, -ef, ef);
       r[NB6 + j] = t - bias[NB6 + j];
       if (P.any_drive) r[NB6 + j] += dforce[j];
+      if constexpr (DFF) if (dff_soa) {
+        // actuation + drive estimate; an implicit drive's -(h kd + h^2 kp)(qd_end - qd) is completed at the end of
+        // the substep, so only its qd half is formed here
+        float f = t;
+        if (P.any_drive) {
+          f += dforce[j];
+          if ((dimplb >> j) & 1u) f += h * (dofp(1, j, M->dkd[j]) + h * dofp(0, j, M->dkp[j])) * s.qd[j];
+        }
+        dff_soa[j * N + e] = f;
+      }
     }
 #pragma unroll
     for (int kk = 0; kk < NV; ++kk) {
@@ -1031,6 +1055,12 @@ GS_HD void substep(const DevModel* __restrict__ Min, const DevParams& P, EnvStat
     s.q[j] += h * nupos[NB6 + j];
     s.qd[j] = nun[NB6 + j];
   }
+  if constexpr (DFF) if (dff_soa && P.any_drive) {
+#pragma unroll
+    for (int j = 0; j < T::ND; ++j)
+      if ((dimplb >> j) & 1u)
+        dff_soa[j * N + e] -= h * (dofp(1, j, M->dkd[j]) + h * dofp(0, j, M->dkp[j])) * s.qd[j];
+  }
   if (collect) {
     // net contact force per reported link of this (collecting) substep, SoA [3*nr][N]
     // (links = bodies unless fixed-joint links are kept: then a candidate adds to its own link)
@@ -1202,7 +1232,7 @@ GS_HD void candidate_centres(const DevModel* __restrict__ Min, const EnvState<T>
 // ---------------------------------------------------------------- per-env entry points
 // gym.simulate for env e: `substeps` substeps with constant dof forces [N][nd] (or zero)
 // REC: the self-collision narrowphase already ran (k_pair_records), its near-pair records are in B.rows
-template <class T, bool TERR, int LB, bool SELF = true, bool REC = false>
+template <class T, bool TERR, int LB, bool SELF = true, bool REC = false, bool DFF = false>
 GS_HD void simulate_env(const DevModel* __restrict__ M, const DevParams& P, const SimBuffers& B,
                         const float* __restrict__ tau_aos, int e, float* lds) {
   const int N = B.N;
@@ -1214,11 +1244,14 @@ GS_HD void simulate_env(const DevModel* __restrict__ M, const DevParams& P, cons
   for (int sstep = 0; sstep < P.substeps; ++sstep) {
     const bool last = (sstep == P.substeps - 1) && P.collect;
     if constexpr (SELF && REC)  // this substep's near-pair records
-      substep<T, TERR, LB, 0, SELF, 1>(M, P, s, tau, B.mu, N, e, lds, B.cf, last,
+      substep<T, TERR, LB, 0, SELF, 1, DFF>(M, P, s, tau, B.mu, N, e, lds, B.cf, last,
                                        sstep == P.substeps - 1 ? B.sens : nullptr, nullptr,
-                                       B.rows + (size_t)e * LaneCfg<T, TERR>::ROW_FLOATS);
+                                       B.rows + (size_t)e * LaneCfg<T, TERR>::ROW_FLOATS,
+                                       sstep == P.substeps - 1 ? P.dof_force : nullptr);
     else
-      substep<T, TERR, LB, 0, SELF>(M, P, s, tau, B.mu, N, e, lds, B.cf, last, sstep == P.substeps - 1 ? B.sens : nullptr);
+      substep<T, TERR, LB, 0, SELF, 0, DFF>(M, P, s, tau, B.mu, N, e, lds, B.cf, last,
+                                            sstep == P.substeps - 1 ? B.sens : nullptr, nullptr, nullptr,
+                                            sstep == P.substeps - 1 ? P.dof_force : nullptr);
   }
   store_state<T>(B.state, N, e, s);
 }
@@ -1278,7 +1311,7 @@ GS_HD void pd_outputs(const DevModel* __restrict__ M, const DevParams& P, const 
 }
 
 // the fused decimation step (gs_pd_args, include/gymsim.h) for env e
-template <class T, bool TERR, int LB, bool SELF = true>
+template <class T, bool TERR, int LB, bool SELF = true, bool DFF = false>
 GS_HD void pd_step_env(const DevModel* __restrict__ M, const DevParams& P, const SimBuffers& B, const PdDev& A, int e,
                        float* lds) {
   const int N = B.N;
@@ -1292,7 +1325,8 @@ GS_HD void pd_step_env(const DevModel* __restrict__ M, const DevParams& P, const
   for (int it = 0; it < total; ++it) {
     if (it < n_pd && (it % sub) == 0) pd_torques<T>(A, e, s, it == 0, tau);
     const bool last = ((it % sub) == sub - 1) && P.collect;
-    substep<T, TERR, LB, 0, SELF>(M, P, s, tau, B.mu, N, e, lds, B.cf, last, it == total - 1 ? B.sens : nullptr);
+    substep<T, TERR, LB, 0, SELF, 0, DFF>(M, P, s, tau, B.mu, N, e, lds, B.cf, last, it == total - 1 ? B.sens : nullptr,
+                                          nullptr, nullptr, it == total - 1 ? P.dof_force : nullptr);
     if (it == n_pd - 1) pd_dof_out<T>(A, e, s);
   }
   pd_outputs<T>(M, P, B, A, e, s, tau);

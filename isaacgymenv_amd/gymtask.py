@@ -135,6 +135,25 @@ class GtAntResetArgs(C.Structure):
                                   "env_ids_out")]
 
 
+class GtFlatParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_envs", "num_dofs", "num_bodies", "base_index", "num_knees")] + [
+        ("knee_idx", C.c_int32 * 8), ("max_episode_length", C.c_int32)] + [
+        (n, C.c_float) for n in ("lin_vel_scale", "ang_vel_scale", "dof_pos_scale", "dof_vel_scale", "rew_lin_vel_xy",
+                                 "rew_ang_vel_z", "rew_torque")]
+
+
+class GtFlatBuffers(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("root_states", "dof_state", "contact_forces", "torques", "actions", "commands",
+                                          "default_dof_pos", "gravity_vec", "obs_buf", "rew_buf", "reset_buf",
+                                          "progress_buf", "reset_count", "host_count")] + [("seq", C.c_int32),
+                                                                                           ("reset_masks", C.c_void_p)]
+
+
+class GtFlatResetArgs(C.Structure):
+    _fields_ = [("plan", GtTorchRandPlan * 5), ("range", C.c_float * 5), ("lower", C.c_float * 5)] + [
+        (n, C.c_void_p) for n in ("dof_state", "commands", "progress_buf", "env_ids_out")]
+
+
 _lib = None
 
 
@@ -255,6 +274,9 @@ def lib():
                            "gt_ant_post_physics": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), vp],
                            "gt_ant_reset_flagged": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), i,
                                                     C.POINTER(GtAntResetArgs), vp],
+                           "gt_flat_post_physics": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), vp],
+                           "gt_flat_reset_flagged": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), i,
+                                                     C.POINTER(GtFlatResetArgs), vp],
                            "gt_anymal_reset_observe": [P, B, i, C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
                                                        C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp, vp,
                                                        vp, vp],
@@ -275,7 +297,7 @@ EXPORTED_SYMBOLS = ["gt_abi_version", "gt_last_error", "gt_anymal_post_physics_a
                     "gt_anymal_post_physics_b", "gt_anymal_reset_flagged", "gt_torch_rand", "gt_host_alloc",
                     "gt_host_free", "gt_wait_host_seq", "gt_measure_heights", "gt_hound_control",
                     "gt_ant_post_physics", "gt_ant_reset_flagged", "gt_anymal_reset_observe", "gt_anymal_post_physics_ab",
-                    "gt_anymal_wait_reset_observe"]
+                    "gt_anymal_wait_reset_observe", "gt_flat_post_physics", "gt_flat_reset_flagged"]
 
 
 class AntTailKernel:
@@ -372,6 +394,102 @@ class AntTailKernel:
         b = self._buffers()
         stream = raw_stream(t.root_states.device)
         _check(lib().gt_ant_post_physics(C.byref(self.p), C.byref(b), C.c_void_p(stream)), "gt_ant_post_physics")
+        self._launched = True
+
+
+class FlatTailKernel:
+    """gt_flat_post_physics / gt_flat_reset_flagged bound to one Anymal or Hound env (tasks/anymal.py, GPU pipeline):
+    observations + reward + done mask in one launch with the done count published to pinned host memory, and
+    reset_idx of the flagged envs in one launch plus the one-call indexed state set."""
+
+    def __init__(self, env):
+        L = lib()
+        t = self.env = env
+        p = GtFlatParams()
+        p.num_envs, p.num_dofs, p.num_bodies = t.num_envs, t.num_dof, int(t.contact_forces.shape[1])
+        knees = [int(v) for v in t.knee_indices.cpu()]
+        if len(knees) > 8:
+            raise RuntimeError(f"gt_flat_post_physics takes at most 8 knee links, the asset has {len(knees)}")
+        p.base_index, p.num_knees = int(t.base_index), len(knees)
+        p.knee_idx[:len(knees)] = knees
+        p.max_episode_length = int(t.max_episode_length)
+        p.lin_vel_scale, p.ang_vel_scale = float(t.lin_vel_scale), float(t.ang_vel_scale)
+        p.dof_pos_scale, p.dof_vel_scale = float(t.dof_pos_scale), float(t.dof_vel_scale)
+        p.rew_lin_vel_xy, p.rew_ang_vel_z = float(t.rew_scales["lin_vel_xy"]), float(t.rew_scales["ang_vel_z"])
+        p.rew_torque = float(t.rew_scales["torque"])
+        self.p = p
+        self.reset_count = torch.zeros(3, dtype=torch.int32, device=t.device)
+        h, d = C.c_void_p(), C.c_void_p()
+        _check(L.gt_host_alloc(8, C.byref(h), C.byref(d)), "gt_host_alloc")
+        self._host_words, self._host_words_dev = h.value, d.value
+        self._seq = 0
+        self._launched = False
+        self._count = C.c_int32(0)
+        self.reset_masks = torch.zeros((t.num_envs + 63) // 64, dtype=torch.int64, device=t.device)
+        self.env_ids = torch.zeros(t.num_envs, dtype=torch.int32, device=t.device)
+        self.planner = TorchRandPlanner(t.device)
+
+    def __del__(self):
+        if getattr(self, "_host_words", None) and _lib is not None:
+            _lib.gt_host_free(self._host_words)
+            self._host_words = None
+
+    def done_count(self):
+        """Envs the previous launch flagged (None before the first launch: the caller must look)."""
+        if not self._launched:
+            return None
+        _check(lib().gt_wait_host_seq(C.c_void_p(self._host_words), self._seq, 10000, C.byref(self._count)),
+               "gt_wait_host_seq")
+        return int(self._count.value)
+
+    def reset_flagged(self, k: int):
+        """anymal.py:278-304 reset_idx for the k envs the previous launch flagged: the five torch_rand_float draws
+        evaluated in-kernel from the device generator (advanced exactly as the five torch.rand calls would), the dof
+        state, commands and counters, then the reference's two indexed state sets.  Returns the env ids (int32 [k])."""
+        from .isaacgym import gymtorch
+        t = self.env
+        r = GtFlatResetArgs()
+        nd = t.num_dof
+        for i, plan in enumerate(self.planner.plan_many((k * nd, k * nd, k, k, k))):
+            r.plan[i] = plan
+        # torch_rand_float(lower, upper): (upper - lower) * rand + lower, the range a Python double
+        bounds = ((0.5, 1.5), (-0.1, 0.1), tuple(t.command_x_range), tuple(t.command_y_range), tuple(t.command_yaw_range))
+        for i, (lo, hi) in enumerate(bounds):
+            r.range[i], r.lower[i] = hi - lo, lo
+        r.dof_state, r.commands = t.dof_state.data_ptr(), t.commands.data_ptr()
+        r.progress_buf, r.env_ids_out = t.progress_buf.data_ptr(), self.env_ids.data_ptr()
+        stream = raw_stream(t.root_states.device)
+        _check(lib().gt_flat_reset_flagged(C.byref(self.p), C.byref(self._buffers()), k, C.byref(r),
+                                           C.c_void_p(stream)), "gt_flat_reset_flagged")
+        ids = self.env_ids[:k]
+        t.gym.amd_set_root_and_dof_state_indexed(t.sim, gymtorch.unwrap_tensor(t.initial_root_states),
+                                                 gymtorch.unwrap_tensor(t.dof_state), gymtorch.unwrap_tensor(ids), k)
+        return ids
+
+    def _buffers(self):
+        t = self.env
+        b = GtFlatBuffers()
+        for name, ten in (("root_states", t.root_states), ("dof_state", t.dof_state),
+                          ("contact_forces", t.contact_forces), ("torques", t.torques), ("actions", t.actions),
+                          ("commands", t.commands), ("default_dof_pos", t.default_dof_pos),
+                          ("gravity_vec", t.gravity_vec), ("obs_buf", t.obs_buf), ("rew_buf", t.rew_buf),
+                          ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf)):
+            assert ten.is_contiguous() and ten.is_cuda, name
+            setattr(b, name, ten.data_ptr())
+        assert t.reset_buf.dtype == torch.int64 and t.progress_buf.dtype == torch.int64
+        assert t.actions.dtype == torch.float32 and t.actions.shape == t.torques.shape
+        b.seq = self._seq
+        b.reset_count = self.reset_count.data_ptr()
+        b.host_count = self._host_words_dev
+        b.reset_masks = self.reset_masks.data_ptr()
+        return b
+
+    def __call__(self):
+        t = self.env
+        self._seq += 1
+        b = self._buffers()
+        stream = raw_stream(t.root_states.device)
+        _check(lib().gt_flat_post_physics(C.byref(self.p), C.byref(b), C.c_void_p(stream)), "gt_flat_post_physics")
         self._launched = True
 
 

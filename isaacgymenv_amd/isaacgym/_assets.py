@@ -738,6 +738,9 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
 PACKED_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
 PACKED_INDEX = {
     "anymal_minimal.urdf": "anymal_c.model.json",
+    # (anymal.py loads urdf/anymal_c/urdf/anymal.urdf: the packed model is the minimal one, the robot every compiled
+    # anymal_c kernel is built for)
+    "anymal.urdf": "anymal_c.model.json",
     "cartpole.urdf": "cartpole.model.json",
     "Hound.urdf": "hound.model.json",
     "nv_ant.xml": "nv_ant.model.json",

@@ -101,6 +101,8 @@ def lib():
             "gs_sim_set_root_and_dof": (i, [vp, vp, vp, vp, i, vp]),
             "gs_sim_set_self_collision": (i, [vp, i]),
             "gs_sim_refresh_force_sensor": (i, [vp, vp, vp]),
+            "gs_sim_bind_dof_force": (i, [vp, vp]),
+            "gs_sim_refresh_dof_force": (i, [vp, vp, vp]),
             "gs_sim_add_triangle_mesh": (i, [vp, vp, C.c_int64, vp, C.c_int64, vp, d, d, d]),
             "gs_debug_terrain_query": (i, [vp, vp, vp, i, vp, vp]),
             "gs_debug_self_contacts": (i, [vp, i, vp, vp, vp]),
@@ -126,6 +128,7 @@ EXPORTED_SYMBOLS = [
     "gs_sim_refresh_dof", "gs_sim_refresh_contact", "gs_sim_set_root", "gs_sim_set_dof", "gs_sim_pd_step",
     "gs_sim_kernel_variant", "gs_sim_enable_timing", "gs_sim_last_kernel_ms", "gs_debug_phase_cycles",
     "gs_sim_set_force_sensors", "gs_sim_bind_force_sensors", "gs_sim_refresh_force_sensor",
+    "gs_sim_bind_dof_force", "gs_sim_refresh_dof_force",
     "gs_sim_add_triangle_mesh", "gs_debug_terrain_query", "gs_sim_refresh_rigid_body", "gs_sim_refresh_jacobian",
     "gs_sim_refresh_mass_matrix", "gs_sim_set_dof_drives", "gs_sim_bind_dof_targets", "gs_sim_set_self_collision",
     "gs_debug_self_contacts", "gs_debug_team_form", "gs_debug_team_sweeps", "gs_sim_bind_dof_properties_env", "gs_sim_pd_tail_supported", "gs_sim_set_root_and_dof",

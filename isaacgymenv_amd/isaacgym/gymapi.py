@@ -446,6 +446,8 @@ class Sim:
             self._cf_dev = torch.zeros(N * nb, 3, dtype=f32, device=dev)
             self._sens_dev = torch.zeros(N * len(sens), 6, dtype=f32, device=dev)
         self.prepared = True
+        if self.dof_force_tensor is not None:  # acquired before prepare_sim
+            self._bind_dof_force()
         self.refresh("root")
         self.refresh("dof")
         self.refresh("contact")
@@ -553,8 +555,38 @@ class Sim:
         self.dof_tensor = torch.zeros(N * nd, 2, dtype=f32, device=tdev)
         self.contact_tensor = torch.zeros(N * nb, 3, dtype=f32, device=tdev)
         self.rb_tensor = self.jac_tensor = self.mm_tensor = None
+        self.dof_force_tensor = None  # acquire_dof_force_tensor
 
     # -------- tensor API
+    def dof_force_sensor_tensor(self):
+        """The sim-owned DOF force tensor [N*nd], allocated on first acquire; the solver starts
+        writing it (gs_sim_bind_dof_force) then, or at prepare_sim when acquired earlier."""
+        import torch
+        self._tensors()
+        if self.dof_force_tensor is None:
+            self.dof_force_tensor = torch.zeros(self.num_envs * self.num_dofs, dtype=torch.float32,
+                                                device=self.tensor_device)
+            if self.prepared:
+                self._bind_dof_force()
+        return self.dof_force_tensor
+
+    def _bind_dof_force(self):
+        import torch
+        N, nd, dev = self.num_envs, self.num_dofs, self.sim_device
+        self.dof_force_soa = torch.zeros(max(1, nd), N, dtype=torch.float32, device=dev)
+        if not self.gpu_pipeline and not self.host:
+            self._dof_force_dev = torch.zeros(N * nd, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().gs_sim_bind_dof_force(self.handle, self.dof_force_soa.data_ptr()), "gs_sim_bind_dof_force")
+
+    def refresh_dof_force(self):
+        dst = self.dof_force_tensor
+        if dst is None or not self.prepared:
+            return  # never acquired: nothing to fill
+        out = dst if self.gpu_pipeline or self.host else self._dof_force_dev
+        _lib.check(_lib.lib().gs_sim_refresh_dof_force(self.handle, out.data_ptr(), self.stream()), "refresh dof force")
+        if out is not dst:
+            dst.copy_(out.cpu())
+
     def kinematics_tensor(self, kind: str):
         """Sim-owned rigid-body-state / jacobian / mass-matrix tensors, allocated on first acquire
         and filled once (Isaac Gym's acquired tensors hold the prepared state)."""
@@ -888,6 +920,11 @@ class Gym:
         """[num_envs * sensors_per_env, 6]: force (3) then torque (3) in the sensor frame (ant.py:80-83)."""
         return GymTensor(sim.sensor_tensor, "sensor")
 
+    def acquire_dof_force_tensor(self, sim: Sim) -> GymTensor:
+        """[num_envs * num_dofs]: the force the solver applied at each dof in the last substep of the last simulate --
+        the effort-clamped actuation force plus the joint drive's force (anymal.py:95)."""
+        return GymTensor(sim.dof_force_sensor_tensor(), "dof_force")
+
     def acquire_jacobian_tensor(self, sim: Sim, name: str) -> GymTensor:
         """Floating base: [num_envs, num_bodies, 6, 6 + num_dofs]; fixed base: [num_envs, num_bodies - 1,
         6, num_dofs] (the welded root row dropped, as Isaac Gym does).  Rows: COM linear velocity (3),
@@ -931,7 +968,7 @@ class Gym:
             sim.refresh("sensor")
 
     def refresh_dof_force_tensor(self, sim: Sim):
-        return None
+        sim.refresh_dof_force()  # (a no-op unless acquire_dof_force_tensor was called)
 
     # ---- set (caller -> sim)
     def set_dof_actuation_force_tensor(self, sim: Sim, t: GymTensor) -> bool:

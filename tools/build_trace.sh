@@ -9,7 +9,7 @@ mkdir -p $OUT
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-slp-vectorize -DGS_GJK_TRACE=$1 -I $ROOT/include -I $CS"
 pids=()
 for T in $(python3 -c "import sys; sys.path.insert(0, '$ROOT'); from isaacgymenv_amd.build import topologies; print(' '.join(topologies()))"); do
-  for F in 0 1 2 3; do
+  for F in 0 1 2 3 4 5 6 7; do
     /opt/rocm/bin/hipcc $FL -DGS_INST_TOPO=$T -DGS_INST_FORM=$F -c $CS/gs_phys_inst.hip -o $OUT/inst_${T}_$F.o & pids+=($!)
   done
 done
