@@ -34,8 +34,8 @@ SIM_FLAGS = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"libgymtask.so": ["-ffp-contract=off"], "libgymrl.so": ["-ffp-contract=off"], "libgymsim.so": SIM_FLAGS,
                "libgymsim_prof.so": SIM_FLAGS + ["-DGS_PHASE_PROFILE"]}
 HEADERS = ["gs_internal.h", "gs_topologies.h", "gs_math.h", "gs_terrain.h", "gs_pairs.h", "gs_solver.h", "gs_kinematics.h", "gs_host_impl.h",
-           "gs_physics_impl.h", "torch_philox.h", "gt_anymal_tail.h", "gs_kernel_choice.h", "gs_model_pack.h",
-           "gs_terrain_build.h"]
+           "gs_physics_impl.h", "torch_philox.h", "gt_anymal_tail.h", "gt_wave.h", "gt_host.h", "gs_kernel_choice.h",
+           "gs_model_pack.h", "gs_terrain_build.h"]
 # gs_phys_inst.hip is compiled once per (topology, kernel form): 0 simulate plane, 1 simulate terrain-mesh,
 # 2 fused PD step plane, 3 fused PD step terrain-mesh (gs_physics_impl.h); 4-7 the same four with the DOF force
 # store compiled in (launched only while a sim has the tensor bound)

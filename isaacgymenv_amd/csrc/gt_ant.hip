@@ -12,14 +12,16 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/gymtask.h"
 #include "torch_philox.h"
-
-void gt_set_last_error(const char* msg);
+#include "gt_anymal_tail.h"
+#include "gt_host.h"
 
 namespace {
+
+using gt_tail::quat_rotate;
+using gt_tail::quat_rotate_inverse;
 
 constexpr float kTwoPi = 6.2831854820251465f;  // float(2*np.pi) as torch casts it for a float32 tensor
 
@@ -44,22 +46,6 @@ __device__ __forceinline__ void quat_mul(const float* a, const float* b, float* 
   o[2] = qq - zz + (z1 + y1) * (w2 - x2);
 }
 
-// quat_rotate (sign +1) / quat_rotate_inverse (sign -1): a +- b + c with a = v (2 w^2 - 1),
-// b = (u x v) w 2, c = u (u . v) 2
-__device__ __forceinline__ void quat_rot(const float* q, const float* v, bool inverse, float* o) {
-  const float w = q[3];
-  const float s = 2.0f * (w * w) - 1.0f;
-  const float cx = q[1] * v[2] - q[2] * v[1];
-  const float cy = q[2] * v[0] - q[0] * v[2];
-  const float cz = q[0] * v[1] - q[1] * v[0];
-  const float d = q[0] * v[0] + q[1] * v[1] + q[2] * v[2];
-  const float b[3] = {cx * w * 2.0f, cy * w * 2.0f, cz * w * 2.0f};
-  const float a[3] = {v[0] * s, v[1] * s, v[2] * s};
-  const float c[3] = {q[0] * d * 2.0f, q[1] * d * 2.0f, q[2] * d * 2.0f};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) o[k] = inverse ? a[k] - b[k] + c[k] : a[k] + b[k] + c[k];
-}
-
 __global__ void __launch_bounds__(64) k_ant_tail(gt_ant_params p, gt_ant_buffers b) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   bool done = false;
@@ -80,14 +66,14 @@ __global__ void __launch_bounds__(64) k_ant_tail(gt_ant_params p, gt_ant_buffers
     quat_mul(rs + 3, b.inv_start_rot + (size_t)e * 4, tq);
     const float vec0[3] = {1.0f, 0.0f, 0.0f}, vec1[3] = {0.0f, 0.0f, 1.0f};
     float up[3], hd[3];
-    quat_rot(tq, vec1, false, up);
-    quat_rot(tq, vec0, false, hd);
+    quat_rotate(tq, vec1, up);
+    quat_rotate(tq, vec0, hd);
     const float up_proj = up[2];
     const float heading_proj = hd[0] * tdir[0] + hd[1] * tdir[1] + hd[2] * tdir[2];
     // compute_rot (torch_jit_utils.py:266-277): local velocities, roll / yaw, angle to target
     float vl[3], avl[3];
-    quat_rot(tq, rs + 7, true, vl);
-    quat_rot(tq, rs + 10, true, avl);
+    quat_rotate_inverse(tq, rs + 7, vl);
+    quat_rotate_inverse(tq, rs + 10, avl);
     const float x = tq[0], y = tq[1], z = tq[2], w = tq[3];
     const float roll = py_mod(atan2f(2.0f * (w * x + y * z), w * w - x * x - y * y + z * z), kTwoPi);
     const float yaw = py_mod(atan2f(2.0f * (w * z + x * y), w * w + x * x - y * y - z * z), kTwoPi);
@@ -147,47 +133,17 @@ __global__ void __launch_bounds__(64) k_ant_tail(gt_ant_params p, gt_ant_buffers
     b.true_objective[e] = rs[7];
     done = r != 0;
   }
-  // done count: one 64-bit atomic per wave {waves done << 32 | count}; the grid's last wave publishes
-  // {count, seq} to host memory and re-arms the accumulator (the protocol of gt_anymal_post_physics_a)
-  const unsigned long long m = __ballot(done);
-  if (b.reset_masks && (threadIdx.x & 63) == 0) b.reset_masks[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = m;
-  if ((threadIdx.x & 63) == 0) {
-    const unsigned nwaves = (gridDim.x * blockDim.x + 63) / 64;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(b.reset_count);
-    const unsigned long long add = (1ull << 32) | (unsigned long long)__popcll(m);
-    const unsigned long long old = atomicAdd(acc, add);
-    if ((unsigned)(old >> 32) == nwaves - 1) {
-      const int total = (int)((old + add) & 0xffffffffull);
-      atomicExch(acc, 0ull);
-      b.reset_count[2] = total;
-      if (b.host_count) {
-        // {count, seq} as ONE 8-byte store: the host reads only this word, so no release fence
-        // (a system-scope release writes back the whole L2, microseconds at the end of the tail)
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(b.host_count),
-                           ((unsigned long long)(uint32_t)b.seq << 32) | (uint32_t)total, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  gt_wave::record_done(b, done, (unsigned)e >> 6, (gridDim.x * blockDim.x + 63) / 64);
 }
 
 // reset_idx of the flagged envs (gymtask.h gt_ant_reset_flagged): one lane per env, one wave per workgroup;
 // a flagged env's rank among all flagged envs is the exclusive prefix of the earlier waves' ballot popcounts
+// (gt_wave.h flagged_rank)
 __global__ void __launch_bounds__(64) k_ant_reset_flagged(gt_ant_params p, gt_ant_buffers b, gt_ant_reset_args r) {
   constexpr int ND = 8;
   const int lane = threadIdx.x, w = blockIdx.x, e = w * 64 + lane;
-  int base = 0;
-  for (int c = 0; c < w; c += 64) {
-    const int i = c + lane;
-    base += wave_sum_i(i < w ? (int)__popcll(b.reset_masks[i]) : 0);
-  }
-  const unsigned long long mine = b.reset_masks[w];
+  int base;
+  const unsigned long long mine = gt_wave::flagged_rank(b.reset_masks, w, lane, base);
   if (e >= p.num_envs || !((mine >> lane) & 1ull)) return;
   const int t = base + (int)__popcll(mine & ((1ull << lane) - 1ull));
   float* ds = r.dof_state + (size_t)e * ND * 2;
@@ -226,14 +182,7 @@ extern "C" int gt_ant_reset_flagged(const gt_ant_params* p, const gt_ant_buffers
   }
   if (k == 0) return 0;
   hipLaunchKernelGGL(k_ant_reset_flagged, dim3((p->num_envs + 63) / 64), dim3(64), 0, (hipStream_t)stream, *p, *b, *r);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "gt_ant_reset_flagged: %s", hipGetErrorString(e));
-    gt_set_last_error(buf);
-    return -1;
-  }
-  return 0;
+  return gt_launched("gt_ant_reset_flagged");
 }
 
 extern "C" int gt_ant_post_physics(const gt_ant_params* p, const gt_ant_buffers* b, void* stream) {
@@ -246,12 +195,5 @@ extern "C" int gt_ant_post_physics(const gt_ant_params* p, const gt_ant_buffers*
   }
   const int blocks = (p->num_envs + 63) / 64;
   hipLaunchKernelGGL(k_ant_tail, dim3(blocks), dim3(64), 0, (hipStream_t)stream, *p, *b);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "gt_ant_post_physics: %s", hipGetErrorString(e));
-    gt_set_last_error(buf);
-    return -1;
-  }
-  return 0;
+  return gt_launched("gt_ant_post_physics");
 }

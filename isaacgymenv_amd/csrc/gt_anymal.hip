@@ -17,8 +17,9 @@
 #include "../../include/gymtask.h"
 #include "torch_philox.h"
 #include "gt_anymal_tail.h"
+#include "gt_host.h"
 
-// k_reset_flagged's episode-sum hand-off depends on gfx950's L2-served agent-scope atomics (see there)
+// k_reset_flagged's episode-sum hand-off depends on gfx950's sc1 agent-scope atomic stores and loads (see there)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "gt_anymal.hip targets gfx950 only (the k_reset_flagged hand-off ordering is gfx950's)"
 #endif
@@ -27,7 +28,7 @@ namespace {
 thread_local std::string g_err;
 
 using namespace gt_tail;
-
+using namespace gt_wave;
 
 // One lane per env, one wave per workgroup (4096 envs -> 64 workgroups on 64 CUs: the tail is
 // latency bound, so spreading it over CUs beats packing 4 waves per CU).
@@ -36,12 +37,8 @@ __global__ void __launch_bounds__(64) k_post_a(gt_anymal_params p, gt_anymal_buf
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   bool reset = false;
   if (e < p.num_envs) reset = post_a_env<VEC, HOUND, NDC>(p, b, h, e);
-  // reset count (gt_tail::publish_count) and this wave's 64-bit mask of flagged envs (k_reset_flagged ranks them)
-  const unsigned long long m = __ballot(reset);
-  if ((threadIdx.x & 63) == 0) {
-    if (b.reset_masks) b.reset_masks[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = m;
-    publish_count(b, (unsigned)__popcll(m), (gridDim.x * blockDim.x + 63) / 64);
-  }
+  // the reset count and this wave's 64-bit mask of flagged envs (k_reset_flagged ranks them)
+  record_done(b, reset, (unsigned)e >> 6, (gridDim.x * blockDim.x + 63) / 64);
 }
 
 // k_post_a with a gt_anymal_variant (gymtask.h ABI 6; post_a_env's VAR form): a kernel of its own, so that the
@@ -51,11 +48,7 @@ __global__ void __launch_bounds__(64) k_post_a_var(gt_anymal_params p, gt_anymal
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   bool reset = false;
   if (e < p.num_envs) reset = post_a_env<VEC, false, NDC, true>(p, b, gt_anymal_hound{}, e, v);
-  const unsigned long long m = __ballot(reset);
-  if ((threadIdx.x & 63) == 0) {
-    if (b.reset_masks) b.reset_masks[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = m;
-    publish_count(b, (unsigned)__popcll(m), (gridDim.x * blockDim.x + 63) / 64);
-  }
+  record_done(b, reset, (unsigned)e >> 6, (gridDim.x * blockDim.x + 63) / 64);
 }
 
 __global__ void k_reset(gt_anymal_params p, gt_anymal_buffers b, const int32_t* __restrict__ ids, int k,
@@ -89,17 +82,6 @@ __global__ void k_reset(gt_anymal_params p, gt_anymal_buffers b, const int32_t* 
   const size_t N = p.num_envs;
   // the episode sums were summed by k_episode_sums (launched before this kernel)
   for (int term = 0; term < GT_ANYMAL_NUM_TERMS; ++term) b.episode_sums[term * N + e] = 0.0f;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // ep[term] = sum over t of episode_sums[term][ids[t]] in a FIXED order (extras["episode"] must not
@@ -169,12 +151,8 @@ __global__ void __launch_bounds__(64) k_reset_flagged(gt_anymal_params p, gt_any
   const int lane = threadIdx.x;
   const int w = blockIdx.x;
   const int e = w * 64 + lane;
-  int base = 0;
-  for (int c = 0; c < w; c += 64) {
-    const int i = c + lane;
-    base += wave_sum(i < w ? (int)__popcll(b.reset_masks[i]) : 0);
-  }
-  const unsigned long long mine = b.reset_masks[w];
+  int base;
+  const unsigned long long mine = flagged_rank(b.reset_masks, w, lane, base);
   const bool flagged = (mine >> lane) & 1ull;
   const int nd = p.num_dofs;
   const int na = HOUND ? h.num_actions : nd;
@@ -286,10 +264,12 @@ __global__ void __launch_bounds__(64) k_reset_flagged(gt_anymal_params p, gt_any
   // each wave waits for its own stores before ONE lane adds to the unsharded counter, and the wave
   // whose add returned last loads.  No __threadfence(): two of those per wave (~3.5 us each) were
   // most of this kernel's time.
-  // The ordering this hand-off relies on is gfx950's (agent-scope relaxed atomics are served by L2, the one
-  // coherence point of the agent; vmcnt(0) retires this wave's stores there before its counter add; the last
-  // wave's loads read L2): under the scoped C++ model a release on the add and an acquire in the last wave would be
-  // needed, at the cost of the cache write-back / invalidate above.  The build is gfx950-only (the #error below).
+  // The ordering this hand-off relies on is gfx950's: the slots' stores and loads are sc1 agent-scope atomics (the
+  // stores write through their XCD's L2 and the loads bypass L1 and fetch at agent scope: MI355X has one L2 per XCD,
+  // so no single L2 is the agent's coherence point), and vmcnt(0) retires this wave's stores before its counter add,
+  // which the last wave's loads follow.  Under the scoped C++ model a release on the add and an acquire in the last
+  // wave would be needed, at the cost of the cache write-back / invalidate above.  The build is gfx950-only (the
+  // #error at the top of this file).
   // slot NT (terrain): the wave's sum of terrain levels after the update, for mean(terrain_levels)
   constexpr int NT = GT_ANYMAL_NUM_TERMS + 1;
 #pragma unroll
@@ -457,7 +437,7 @@ __device__ __forceinline__ void post_ab_run(const gt_anymal_params& p, const gt_
     slices[e0 / kAbEnvs] = (uint16_t)(m & 0xffffull);
     if (e0 + kAbEnvs >= N)  // the last workgroup clears its mask word's slices past the last env
       for (int q = e0 / kAbEnvs + 1; q % 4 != 0; ++q) slices[q] = 0;
-    publish_count(b, (unsigned)__popcll(m & 0xffffull), gridDim.x);
+    publish_done_count(b, (unsigned)__popcll(m & 0xffffull), gridDim.x);
   }
   __syncthreads();
   const int no = p.num_obs, ne = (N - e0 < kAbEnvs ? N - e0 : kAbEnvs);
@@ -563,8 +543,12 @@ int check_params(const gt_anymal_params* p, const gt_anymal_buffers* b) {
 gt_anymal_hound hound_of(const gt_anymal_buffers* b) { return b->hound ? *b->hound : gt_anymal_hound{}; }
 }  // namespace
 
-// shared with the other task kernels of libgymtask (gt_hound.hip)
+// gt_host.h: shared with the other task kernels of libgymtask
 void gt_set_last_error(const char* msg) { g_err = msg; }
+int gt_launched(const char* where) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(where, e);
+}
 
 extern "C" {
 
@@ -596,8 +580,7 @@ int gt_anymal_post_physics_a(const gt_anymal_params* p, const gt_anymal_buffers*
     hipLaunchKernelGGL((k_post_a<true, false, 12>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
   else if (vec) hipLaunchKernelGGL((k_post_a<true, false>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
   else hipLaunchKernelGGL((k_post_a<false, false>), grid, dim3(blk), 0, (hipStream_t)stream, *p, *b, h);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_anymal_post_physics_a", e);
+  return gt_launched("gt_anymal_post_physics_a");
 }
 
 int gt_anymal_reset(const gt_anymal_params* p, const gt_anymal_buffers* b, const int32_t* env_ids, int k,
@@ -618,8 +601,7 @@ int gt_anymal_reset(const gt_anymal_params* p, const gt_anymal_buffers* b, const
   const int blk = 256;
   hipLaunchKernelGGL(k_reset, dim3((k + blk - 1) / blk), dim3(blk), 0, st, *p, *b, env_ids, k, pos_offset, dof_vel,
                      cmd_x, cmd_y, cmd_heading);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_anymal_reset", e);
+  return gt_launched("gt_anymal_reset");
 }
 
 int gt_anymal_post_physics_ab(const gt_anymal_params* p, const gt_anymal_buffers* b,
@@ -645,8 +627,7 @@ int gt_anymal_post_physics_ab(const gt_anymal_params* p, const gt_anymal_buffers
     else hipLaunchKernelGGL((k_post_ab_var<0>), g, bl, 0, (hipStream_t)stream, *p, *b, v, nullptr, pl);
   } else if (noise_plan) hipLaunchKernelGGL((k_post_ab<2>), g, bl, 0, (hipStream_t)stream, *p, *b, nullptr, pl);
   else hipLaunchKernelGGL((k_post_ab<0>), g, bl, 0, (hipStream_t)stream, *p, *b, nullptr, pl);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_anymal_post_physics_ab", e);
+  return gt_launched("gt_anymal_post_physics_ab");
 }
 
 int gt_anymal_post_physics_b(const gt_anymal_params* p, const gt_anymal_buffers* b, const float* noise,
@@ -675,8 +656,7 @@ int gt_anymal_post_physics_b(const gt_anymal_params* p, const gt_anymal_buffers*
     if (mode == 1) GT_POST_B(1, false); else if (mode == 2) GT_POST_B(2, false); else GT_POST_B(0, false);
   }
 #undef GT_POST_B
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_anymal_post_physics_b", e);
+  return gt_launched("gt_anymal_post_physics_b");
 }
 
 int gt_anymal_reset_flagged(const gt_anymal_params* p, const gt_anymal_buffers* b, int k,
@@ -709,8 +689,7 @@ int gt_anymal_reset_flagged(const gt_anymal_params* p, const gt_anymal_buffers* 
   else
     hipLaunchKernelGGL(k_reset_flagged<false>, g, bl, 0, (hipStream_t)stream, *p, *b, h, k, *d, tr,
                        terrain != nullptr, env_ids_out, episode_out, episode_length_s, partial, done);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_anymal_reset_flagged", e);
+  return gt_launched("gt_anymal_reset_flagged");
 }
 
 int gt_anymal_reset_observe(const gt_anymal_params* p, const gt_anymal_buffers* b, int k, gt_anymal_reset_draws* d,
@@ -764,8 +743,7 @@ int gt_measure_heights(const int16_t* samples, int rows, int cols, float border,
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_measure_heights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, samples,
                      rows, cols, border, hs, vs, root_states, points, num_envs, num_points, heights);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_measure_heights", e);
+  return gt_launched("gt_measure_heights");
 }
 
 int gt_torch_rand(const gt_torch_rand_plan* plan, float* out, void* stream) {
@@ -777,8 +755,7 @@ int gt_torch_rand(const gt_torch_rand_plan* plan, float* out, void* stream) {
   const int blk = 256;
   hipLaunchKernelGGL(k_torch_rand, dim3((plan->numel + blk - 1) / blk), dim3(blk), 0, (hipStream_t)stream, *plan,
                      out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail("gt_torch_rand", e);
+  return gt_launched("gt_torch_rand");
 }
 
 int gt_host_alloc(uint64_t bytes, void** host_ptr, void** device_ptr) {

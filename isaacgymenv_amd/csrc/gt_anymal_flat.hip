@@ -17,33 +17,19 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/gymtask.h"
 #include "torch_philox.h"
-
-void gt_set_last_error(const char* msg);
+#include "gt_anymal_tail.h"
+#include "gt_host.h"
 
 namespace {
 
+using gt_tail::quat_rotate;
+using gt_tail::quat_rotate_inverse;
+
 constexpr int ND = 12;
 constexpr int kObs = 48;
-
-// quat_rotate (inverse = false) / quat_rotate_inverse: a +- b + c with a = v (2 w^2 - 1), b = (u x v) w 2,
-// c = u (u . v) 2
-__device__ __forceinline__ void quat_rot(const float* q, const float* v, bool inverse, float* o) {
-  const float w = q[3];
-  const float s = 2.0f * (w * w) - 1.0f;
-  const float cx = q[1] * v[2] - q[2] * v[1];
-  const float cy = q[2] * v[0] - q[0] * v[2];
-  const float cz = q[0] * v[1] - q[1] * v[0];
-  const float d = q[0] * v[0] + q[1] * v[1] + q[2] * v[2];
-  const float b[3] = {cx * w * 2.0f, cy * w * 2.0f, cz * w * 2.0f};
-  const float a[3] = {v[0] * s, v[1] * s, v[2] * s};
-  const float c[3] = {q[0] * d * 2.0f, q[1] * d * 2.0f, q[2] * d * 2.0f};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) o[k] = inverse ? a[k] - b[k] + c[k] : a[k] + b[k] + c[k];
-}
 
 __device__ __forceinline__ bool link_in_contact(const float* cf, int link) {
   const float* f = cf + (size_t)link * 3;
@@ -57,9 +43,9 @@ __global__ void __launch_bounds__(64) k_flat_tail(gt_flat_params p, gt_flat_buff
     const float* rs = b.root_states + (size_t)e * 13;
     const float quat[4] = {rs[3], rs[4], rs[5], rs[6]};
     float lin[3], ang[3], grav[3];
-    quat_rot(quat, rs + 7, true, lin);
-    quat_rot(quat, rs + 10, true, ang);
-    quat_rot(quat, b.gravity_vec + (size_t)e * 3, false, grav);
+    quat_rotate_inverse(quat, rs + 7, lin);
+    quat_rotate_inverse(quat, rs + 10, ang);
+    quat_rotate(quat, b.gravity_vec + (size_t)e * 3, grav);
     const float* cmd = b.commands + (size_t)e * 3;
     float* ob = b.obs_buf + (size_t)e * kObs;
 #pragma unroll
@@ -98,45 +84,15 @@ __global__ void __launch_bounds__(64) k_flat_tail(gt_flat_params p, gt_flat_buff
     b.reset_buf[e] = r ? 1ll : 0ll;
     done = r;
   }
-  // done count: one 64-bit atomic per wave {waves done << 32 | count}; the grid's last wave publishes
-  // {count, seq} to host memory and re-arms the accumulator (the protocol of gt_ant_post_physics)
-  const unsigned long long m = __ballot(done);
-  if ((threadIdx.x & 63) == 0) {
-    b.reset_masks[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = m;
-    const unsigned nwaves = (gridDim.x * blockDim.x + 63) / 64;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(b.reset_count);
-    const unsigned long long add = (1ull << 32) | (unsigned long long)__popcll(m);
-    const unsigned long long old = atomicAdd(acc, add);
-    if ((unsigned)(old >> 32) == nwaves - 1) {
-      const int total = (int)((old + add) & 0xffffffffull);
-      atomicExch(acc, 0ull);
-      b.reset_count[2] = total;
-      if (b.host_count) {
-        // {count, seq} as ONE 8-byte store: the host reads only this word, so no release fence
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(b.host_count),
-                           ((unsigned long long)(uint32_t)b.seq << 32) | (uint32_t)total, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  gt_wave::record_done(b, done, (unsigned)e >> 6, (gridDim.x * blockDim.x + 63) / 64);
 }
 
 // reset_idx of the flagged envs: one lane per env, one wave per workgroup; a flagged env's rank among all flagged
-// envs is the exclusive prefix of the earlier waves' ballot popcounts (gt_ant.hip k_ant_reset_flagged)
+// envs is the exclusive prefix of the earlier waves' ballot popcounts (gt_wave.h flagged_rank)
 __global__ void __launch_bounds__(64) k_flat_reset_flagged(gt_flat_params p, gt_flat_buffers b, gt_flat_reset_args r) {
   const int lane = threadIdx.x, w = blockIdx.x, e = w * 64 + lane;
-  int base = 0;
-  for (int c = 0; c < w; c += 64) {
-    const int i = c + lane;
-    base += wave_sum_i(i < w ? (int)__popcll(b.reset_masks[i]) : 0);
-  }
-  const unsigned long long mine = b.reset_masks[w];
+  int base;
+  const unsigned long long mine = gt_wave::flagged_rank(b.reset_masks, w, lane, base);
   if (e >= p.num_envs || !((mine >> lane) & 1ull)) return;
   const int t = base + (int)__popcll(mine & ((1ull << lane) - 1ull));
   float* ds = r.dof_state + (size_t)e * ND * 2;
@@ -165,15 +121,6 @@ bool params_ok(const gt_flat_params* p) {
   return true;
 }
 
-int launched(const char* where) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return 0;
-  char buf[256];
-  std::snprintf(buf, sizeof(buf), "%s: %s", where, hipGetErrorString(e));
-  gt_set_last_error(buf);
-  return -1;
-}
-
 }  // namespace
 
 extern "C" int gt_flat_post_physics(const gt_flat_params* p, const gt_flat_buffers* b, void* stream) {
@@ -185,7 +132,7 @@ extern "C" int gt_flat_post_physics(const gt_flat_params* p, const gt_flat_buffe
     return -1;
   }
   hipLaunchKernelGGL(k_flat_tail, dim3((p->num_envs + 63) / 64), dim3(64), 0, (hipStream_t)stream, *p, *b);
-  return launched("gt_flat_post_physics");
+  return gt_launched("gt_flat_post_physics");
 }
 
 extern "C" int gt_flat_reset_flagged(const gt_flat_params* p, const gt_flat_buffers* b, int k, const gt_flat_reset_args* r,
@@ -201,5 +148,5 @@ extern "C" int gt_flat_reset_flagged(const gt_flat_params* p, const gt_flat_buff
   }
   if (k == 0) return 0;
   hipLaunchKernelGGL(k_flat_reset_flagged, dim3((p->num_envs + 63) / 64), dim3(64), 0, (hipStream_t)stream, *p, *b, *r);
-  return launched("gt_flat_reset_flagged");
+  return gt_launched("gt_flat_reset_flagged");
 }

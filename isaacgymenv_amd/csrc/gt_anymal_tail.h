@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/gymtask.h"
+#include "gt_wave.h"
 
 struct gt_anymal_hound;
 
@@ -32,7 +33,19 @@ __device__ __forceinline__ void quat_rotate_inverse(const float* q, const float*
   o[1] = (v[1] * s - (cy * w) * 2.0f) + (q[1] * d) * 2.0f;
   o[2] = (v[2] * s - (cz * w) * 2.0f) + (q[2] * d) * 2.0f;
 }
-
+// reference quat_rotate: a + b + c
+__device__ __forceinline__ void quat_rotate(const float* q, const float* v, float* o) {
+#pragma clang fp contract(off)
+  const float w = q[3];
+  const float s = 2.0f * (w * w) - 1.0f;
+  const float cx = q[1] * v[2] - q[2] * v[1];
+  const float cy = q[2] * v[0] - q[0] * v[2];
+  const float cz = q[0] * v[1] - q[1] * v[0];
+  const float d = q[0] * v[0] + q[1] * v[1] + q[2] * v[2];
+  o[0] = (v[0] * s + (cx * w) * 2.0f) + (q[0] * d) * 2.0f;
+  o[1] = (v[1] * s + (cy * w) * 2.0f) + (q[1] * d) * 2.0f;
+  o[2] = (v[2] * s + (cz * w) * 2.0f) + (q[2] * d) * 2.0f;
+}
 
 __device__ __forceinline__ float sq(float x) { return x * x; }
 __device__ __forceinline__ float norm3(const float* v) {
@@ -306,26 +319,9 @@ __device__ __forceinline__ bool post_a_env(const gt_anymal_params& p, const gt_a
   return reset;
 }
 
-// The done count of one wave (popc envs flagged) joins the launch's total: one 64-bit atomic per wave carries
-// {waves done << 32 | count}; the wave that completes the grid (nwaves waves) publishes the total (device word
-// reset_count[2], and {count, seq} into host memory for the host's spin wait) and re-arms the accumulator.
-// Called by one lane per wave.
+// gt_wave::publish_done_count on a gt_anymal_buffers (the lane-team kernel's call, gs_team.hip).
 __device__ __forceinline__ void publish_count(const gt_anymal_buffers& b, unsigned popc, unsigned nwaves) {
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(b.reset_count);
-  const unsigned long long add = (1ull << 32) | (unsigned long long)popc;
-  const unsigned long long old = atomicAdd(acc, add);
-  if ((unsigned)(old >> 32) == nwaves - 1) {
-    const int total = (int)((old + add) & 0xffffffffull);
-    *acc = 0ull;
-    b.reset_count[2] = total;
-    if (b.host_count) {
-      // {count, seq} as ONE 8-byte store: the host reads only this word, so no release fence
-      // (a system-scope release writes back the whole L2, microseconds at the end of the tail)
-      __hip_atomic_store(reinterpret_cast<unsigned long long*>(b.host_count),
-                         ((unsigned long long)(uint32_t)b.seq << 32) | (uint32_t)total, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  gt_wave::publish_done_count(b, popc, nwaves);
 }
 
 }  // namespace gt_tail

@@ -10,11 +10,9 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/gymtask.h"
-
-void gt_set_last_error(const char* msg);
+#include "gt_host.h"
 
 namespace {
 
@@ -198,12 +196,5 @@ extern "C" int gt_hound_control(const gt_hound_control_params* p, const float* a
   const int blocks = (p->num_envs + 63) / 64;
   hipLaunchKernelGGL(k_hound_control, dim3(blocks), dim3(64), 0, (hipStream_t)stream, *p, actions, dof_state,
                      leg_default, mass_matrix, jacobian, rigid_body, torques, arm_control);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "gt_hound_control: %s", hipGetErrorString(e));
-    gt_set_last_error(buf);
-    return -1;
-  }
-  return 0;
+  return gt_launched("gt_hound_control");
 }

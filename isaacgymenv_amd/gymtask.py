@@ -249,6 +249,42 @@ def _anymal_set_reset_state():
     return AnymalTerrain._set_reset_state
 
 
+def _argtypes():
+    """C argument types of every int-returning export of libgymtask (include/gymtask.h)."""
+    P, B, vp, i = C.POINTER(GtAnymalParams), C.POINTER(GtAnymalBuffers), C.c_void_p, C.c_int
+    return {"gt_anymal_post_physics_a": [P, B, vp],
+            "gt_anymal_reset": [P, B, vp, i, vp, vp, vp, vp, vp, vp, vp],
+            "gt_anymal_post_physics_b": [P, B, vp, C.POINTER(GtTorchRandPlan), vp],
+            "gt_anymal_post_physics_ab": [P, B, C.POINTER(GtTorchRandPlan), vp],
+            "gt_torch_rand": [C.POINTER(GtTorchRandPlan), vp, vp],
+            "gt_anymal_reset_flagged": [P, B, i, C.POINTER(GtAnymalResetDraws),
+                                        C.POINTER(GtAnymalTerrainReset), vp, vp, C.c_float, vp, vp],
+            "gt_host_alloc": [C.c_uint64, C.POINTER(vp), C.POINTER(vp)],
+            "gt_host_free": [vp],
+            "gt_wait_host_seq": [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
+            "gt_measure_heights": [vp, i, i, C.c_float, C.c_float, C.c_float, vp, vp, i, i, vp,
+                                   vp],
+            "gt_hound_control": [C.POINTER(GtHoundControlParams), vp, vp, vp, vp, vp, vp, vp, vp,
+                                 vp],
+            "gt_ant_post_physics": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), vp],
+            "gt_ant_reset_flagged": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), i,
+                                     C.POINTER(GtAntResetArgs), vp],
+            "gt_flat_post_physics": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), vp],
+            "gt_flat_reset_flagged": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), i,
+                                      C.POINTER(GtFlatResetArgs), vp],
+            "gt_anymal_reset_observe": [P, B, i, C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
+                                        C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp, vp,
+                                        vp, vp],
+            "gt_anymal_wait_reset_observe": [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), P, B,
+                                             C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
+                                             C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp,
+                                             vp, vp, vp]}
+
+
+ARGTYPES = _argtypes()
+EXPORTED_SYMBOLS = ["gt_abi_version", "gt_last_error", *ARGTYPES]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -256,34 +292,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m isaacgymenv_amd.build`. "
                                "The GPU pipeline has no torch fallback for the fused task kernels.")
         L = C.CDLL(LIB_PATH)
-        P, B, vp, i = C.POINTER(GtAnymalParams), C.POINTER(GtAnymalBuffers), C.c_void_p, C.c_int
-        for name, args in {"gt_anymal_post_physics_a": [P, B, vp],
-                           "gt_anymal_reset": [P, B, vp, i, vp, vp, vp, vp, vp, vp, vp],
-                           "gt_anymal_post_physics_b": [P, B, vp, C.POINTER(GtTorchRandPlan), vp],
-                           "gt_anymal_post_physics_ab": [P, B, C.POINTER(GtTorchRandPlan), vp],
-                           "gt_torch_rand": [C.POINTER(GtTorchRandPlan), vp, vp],
-                           "gt_anymal_reset_flagged": [P, B, i, C.POINTER(GtAnymalResetDraws),
-                                                       C.POINTER(GtAnymalTerrainReset), vp, vp, C.c_float, vp, vp],
-                           "gt_host_alloc": [C.c_uint64, C.POINTER(vp), C.POINTER(vp)],
-                           "gt_host_free": [vp],
-                           "gt_wait_host_seq": [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
-                           "gt_measure_heights": [vp, i, i, C.c_float, C.c_float, C.c_float, vp, vp, i, i, vp,
-                                                  vp],
-                           "gt_hound_control": [C.POINTER(GtHoundControlParams), vp, vp, vp, vp, vp, vp, vp, vp,
-                                                vp],
-                           "gt_ant_post_physics": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), vp],
-                           "gt_ant_reset_flagged": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), i,
-                                                    C.POINTER(GtAntResetArgs), vp],
-                           "gt_flat_post_physics": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), vp],
-                           "gt_flat_reset_flagged": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), i,
-                                                     C.POINTER(GtFlatResetArgs), vp],
-                           "gt_anymal_reset_observe": [P, B, i, C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
-                                                       C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp, vp,
-                                                       vp, vp],
-                           "gt_anymal_wait_reset_observe": [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), P, B,
-                                                            C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
-                                                            C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp,
-                                                            vp, vp, vp]}.items():
+        for name, args in ARGTYPES.items():
             fn = getattr(L, name)
             fn.restype = C.c_int
             fn.argtypes = args
@@ -293,20 +302,86 @@ def lib():
     return _lib
 
 
-EXPORTED_SYMBOLS = ["gt_abi_version", "gt_last_error", "gt_anymal_post_physics_a", "gt_anymal_reset",
-                    "gt_anymal_post_physics_b", "gt_anymal_reset_flagged", "gt_torch_rand", "gt_host_alloc",
-                    "gt_host_free", "gt_wait_host_seq", "gt_measure_heights", "gt_hound_control",
-                    "gt_ant_post_physics", "gt_ant_reset_flagged", "gt_anymal_reset_observe", "gt_anymal_post_physics_ab",
-                    "gt_anymal_wait_reset_observe", "gt_flat_post_physics", "gt_flat_reset_flagged"]
+class DoneCounter:
+    """The host side of the done-count protocol (csrc/gt_wave.h): the device accumulator reset_count (int32 [3]:
+    the 64-bit accumulator, then the last count), the per-wave ballots reset_masks, the pinned host words a
+    post-physics kernel publishes {count, seq} into, and the sequence number the host waits for."""
+
+    def __init__(self, num_envs, device):
+        self.reset_count = torch.zeros(3, dtype=torch.int32, device=device)
+        self.reset_masks = torch.zeros((num_envs + 63) // 64, dtype=torch.int64, device=device)
+        h, d = C.c_void_p(), C.c_void_p()
+        _check(lib().gt_host_alloc(8, C.byref(h), C.byref(d)), "gt_host_alloc")
+        self.host_words, self.host_words_dev = h.value, d.value
+        self.seq = 0
+        self.out = C.c_int32(0)
+        self._wait = lib().gt_wait_host_seq
+
+    def __del__(self):
+        if getattr(self, "host_words", None) and _lib is not None:
+            _lib.gt_host_free(self.host_words)
+            self.host_words = None
+
+    def next_seq(self) -> int:
+        """The sequence number of the next launch (the struct's int32_t seq: wrapped)."""
+        self.seq = (self.seq + 1) & 0x7FFFFFFF
+        return self.seq
+
+    def wait(self, timeout_ms: int) -> int:
+        """Spin until the launch numbered seq has published; its count."""
+        _check(self._wait(self.host_words, self.seq, timeout_ms, C.byref(self.out)), "gt_wait_host_seq")
+        return int(self.out.value)
+
+    def fill(self, b):
+        b.reset_count = self.reset_count.data_ptr()
+        b.host_count = self.host_words_dev
+        b.reset_masks = self.reset_masks.data_ptr()
 
 
-class AntTailKernel:
+class _FusedTail:
+    """What the Ant and the flat-ground drivers share: one post-physics launch per step (POST, on a BUFFERS struct of
+    the env's tensors()) whose done count the next step's reset asks for."""
+
+    def __init__(self, env, params):
+        self.env, self.p = env, params
+        self._post = getattr(lib(), self.POST)
+        self._done = DoneCounter(env.num_envs, env.device)
+        self.reset_count, self.reset_masks = self._done.reset_count, self._done.reset_masks
+        self._launched = False
+        self.env_ids = torch.zeros(env.num_envs, dtype=torch.int32, device=env.device)
+        self.planner = TorchRandPlanner(env.device)
+
+    def done_count(self):
+        """Envs the previous launch flagged (None before the first launch: the caller must look)."""
+        return self._done.wait(10000) if self._launched else None
+
+    def _buffers(self):
+        t = self.env
+        b = self.BUFFERS()
+        for name, ten in self.tensors():
+            assert ten.is_contiguous() and ten.is_cuda, name
+            setattr(b, name, ten.data_ptr())
+        assert t.reset_buf.dtype == torch.int64 and t.progress_buf.dtype == torch.int64
+        b.seq = self._done.seq
+        self._done.fill(b)
+        return b
+
+    def __call__(self):
+        self._done.next_seq()
+        b = self._buffers()
+        stream = raw_stream(self.env.root_states.device)
+        _check(self._post(C.byref(self.p), C.byref(b), C.c_void_p(stream)), self.POST)
+        self._launched = True
+
+
+class AntTailKernel(_FusedTail):
     """gt_ant_post_physics bound to one Ant env (GPU pipeline): observations + reward + done mask in one
     launch, and the done count published to pinned host memory for the next step's reset."""
 
+    POST, BUFFERS = "gt_ant_post_physics", GtAntBuffers
+
     def __init__(self, env):
-        L = lib()
-        t = self.env = env
+        t = env
         p = GtAntParams()
         p.num_envs, p.num_dofs = t.num_envs, t.num_dof
         p.dt, p.dof_vel_scale, p.contact_force_scale = float(t.dt), float(t.dof_vel_scale), float(t.contact_force_scale)
@@ -317,31 +392,8 @@ class AntTailKernel:
         p.max_episode_length = float(t.max_episode_length)
         p.dof_lower[:] = [float(v) for v in t.dof_limits_lower.cpu()]
         p.dof_upper[:] = [float(v) for v in t.dof_limits_upper.cpu()]
-        self.p = p
+        super().__init__(env, p)
         self.true_objective = torch.zeros(t.num_envs, dtype=torch.float32, device=t.device)
-        self.reset_count = torch.zeros(3, dtype=torch.int32, device=t.device)
-        h, d = C.c_void_p(), C.c_void_p()
-        _check(L.gt_host_alloc(8, C.byref(h), C.byref(d)), "gt_host_alloc")
-        self._host_words, self._host_words_dev = h.value, d.value
-        self._seq = 0
-        self._launched = False
-        self._count = C.c_int32(0)
-        self.reset_masks = torch.zeros((t.num_envs + 63) // 64, dtype=torch.int64, device=t.device)
-        self.env_ids = torch.zeros(t.num_envs, dtype=torch.int32, device=t.device)
-        self.planner = TorchRandPlanner(t.device)
-
-    def __del__(self):
-        if getattr(self, "_host_words", None) and _lib is not None:
-            _lib.gt_host_free(self._host_words)
-            self._host_words = None
-
-    def done_count(self):
-        """Envs the previous launch flagged (None before the first launch: the caller must look)."""
-        if not self._launched:
-            return None
-        _check(lib().gt_wait_host_seq(C.c_void_p(self._host_words), self._seq, 10000, C.byref(self._count)),
-               "gt_wait_host_seq")
-        return int(self._count.value)
 
     def reset_flagged(self, k: int, u_pos=None, u_vel=None):
         """ant.py:252-279 reset_idx for the k envs the previous launch flagged, in one kernel: the two
@@ -370,41 +422,24 @@ class AntTailKernel:
         t.gym.set_dof_state_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.dof_state), gymtorch.unwrap_tensor(ids), k)
         return ids
 
-    def _buffers(self):
+    def tensors(self):
         t = self.env
-        b = GtAntBuffers()
-        for name, ten in (("root_states", t.root_states), ("dof_state", t.dof_state), ("sensors", t.vec_sensor_tensor),
-                          ("actions", t.actions), ("targets", t.targets), ("inv_start_rot", t.inv_start_rot),
-                          ("potentials", t.potentials), ("prev_potentials", t.prev_potentials),
-                          ("up_vec", t.up_vec), ("heading_vec", t.heading_vec), ("obs_buf", t.obs_buf),
-                          ("rew_buf", t.rew_buf), ("true_objective", self.true_objective),
-                          ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf)):
-            assert ten.is_contiguous() and ten.is_cuda, name
-            setattr(b, name, ten.data_ptr())
-        assert t.reset_buf.dtype == torch.int64 and t.progress_buf.dtype == torch.int64
-        b.seq = self._seq
-        b.reset_count = self.reset_count.data_ptr()
-        b.host_count = self._host_words_dev
-        b.reset_masks = self.reset_masks.data_ptr()
-        return b
-
-    def __call__(self):
-        t = self.env
-        self._seq += 1
-        b = self._buffers()
-        stream = raw_stream(t.root_states.device)
-        _check(lib().gt_ant_post_physics(C.byref(self.p), C.byref(b), C.c_void_p(stream)), "gt_ant_post_physics")
-        self._launched = True
+        return (("root_states", t.root_states), ("dof_state", t.dof_state), ("sensors", t.vec_sensor_tensor),
+                ("actions", t.actions), ("targets", t.targets), ("inv_start_rot", t.inv_start_rot),
+                ("potentials", t.potentials), ("prev_potentials", t.prev_potentials), ("up_vec", t.up_vec),
+                ("heading_vec", t.heading_vec), ("obs_buf", t.obs_buf), ("rew_buf", t.rew_buf),
+                ("true_objective", self.true_objective), ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf))
 
 
-class FlatTailKernel:
+class FlatTailKernel(_FusedTail):
     """gt_flat_post_physics / gt_flat_reset_flagged bound to one Anymal or Hound env (tasks/anymal.py, GPU pipeline):
     observations + reward + done mask in one launch with the done count published to pinned host memory, and
     reset_idx of the flagged envs in one launch plus the one-call indexed state set."""
 
+    POST, BUFFERS = "gt_flat_post_physics", GtFlatBuffers
+
     def __init__(self, env):
-        L = lib()
-        t = self.env = env
+        t = env
         p = GtFlatParams()
         p.num_envs, p.num_dofs, p.num_bodies = t.num_envs, t.num_dof, int(t.contact_forces.shape[1])
         knees = [int(v) for v in t.knee_indices.cpu()]
@@ -417,30 +452,7 @@ class FlatTailKernel:
         p.dof_pos_scale, p.dof_vel_scale = float(t.dof_pos_scale), float(t.dof_vel_scale)
         p.rew_lin_vel_xy, p.rew_ang_vel_z = float(t.rew_scales["lin_vel_xy"]), float(t.rew_scales["ang_vel_z"])
         p.rew_torque = float(t.rew_scales["torque"])
-        self.p = p
-        self.reset_count = torch.zeros(3, dtype=torch.int32, device=t.device)
-        h, d = C.c_void_p(), C.c_void_p()
-        _check(L.gt_host_alloc(8, C.byref(h), C.byref(d)), "gt_host_alloc")
-        self._host_words, self._host_words_dev = h.value, d.value
-        self._seq = 0
-        self._launched = False
-        self._count = C.c_int32(0)
-        self.reset_masks = torch.zeros((t.num_envs + 63) // 64, dtype=torch.int64, device=t.device)
-        self.env_ids = torch.zeros(t.num_envs, dtype=torch.int32, device=t.device)
-        self.planner = TorchRandPlanner(t.device)
-
-    def __del__(self):
-        if getattr(self, "_host_words", None) and _lib is not None:
-            _lib.gt_host_free(self._host_words)
-            self._host_words = None
-
-    def done_count(self):
-        """Envs the previous launch flagged (None before the first launch: the caller must look)."""
-        if not self._launched:
-            return None
-        _check(lib().gt_wait_host_seq(C.c_void_p(self._host_words), self._seq, 10000, C.byref(self._count)),
-               "gt_wait_host_seq")
-        return int(self._count.value)
+        super().__init__(env, p)
 
     def reset_flagged(self, k: int):
         """anymal.py:278-304 reset_idx for the k envs the previous launch flagged: the five torch_rand_float draws
@@ -466,31 +478,13 @@ class FlatTailKernel:
                                                  gymtorch.unwrap_tensor(t.dof_state), gymtorch.unwrap_tensor(ids), k)
         return ids
 
-    def _buffers(self):
+    def tensors(self):
         t = self.env
-        b = GtFlatBuffers()
-        for name, ten in (("root_states", t.root_states), ("dof_state", t.dof_state),
-                          ("contact_forces", t.contact_forces), ("torques", t.torques), ("actions", t.actions),
-                          ("commands", t.commands), ("default_dof_pos", t.default_dof_pos),
-                          ("gravity_vec", t.gravity_vec), ("obs_buf", t.obs_buf), ("rew_buf", t.rew_buf),
-                          ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf)):
-            assert ten.is_contiguous() and ten.is_cuda, name
-            setattr(b, name, ten.data_ptr())
-        assert t.reset_buf.dtype == torch.int64 and t.progress_buf.dtype == torch.int64
         assert t.actions.dtype == torch.float32 and t.actions.shape == t.torques.shape
-        b.seq = self._seq
-        b.reset_count = self.reset_count.data_ptr()
-        b.host_count = self._host_words_dev
-        b.reset_masks = self.reset_masks.data_ptr()
-        return b
-
-    def __call__(self):
-        t = self.env
-        self._seq += 1
-        b = self._buffers()
-        stream = raw_stream(t.root_states.device)
-        _check(lib().gt_flat_post_physics(C.byref(self.p), C.byref(b), C.c_void_p(stream)), "gt_flat_post_physics")
-        self._launched = True
+        return (("root_states", t.root_states), ("dof_state", t.dof_state), ("contact_forces", t.contact_forces),
+                ("torques", t.torques), ("actions", t.actions), ("commands", t.commands),
+                ("default_dof_pos", t.default_dof_pos), ("gravity_vec", t.gravity_vec), ("obs_buf", t.obs_buf),
+                ("rew_buf", t.rew_buf), ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf))
 
 
 class HoundControlKernel:
@@ -548,7 +542,6 @@ class AnymalTailKernels:
              "base_height", "air_time", "collision", "stumble", "action_rate", "hip"]
 
     def __init__(self, task):
-        L = lib()
         self.task = t = task
         dev = t.device
         N = t.num_envs
@@ -596,17 +589,12 @@ class AnymalTailKernels:
             t.episode_sums[name] = self.sums[k]
         self.ep_out = z(len(self.TERMS))
         self.noise_scale = t.noise_scale_vec.contiguous()
-        self.reset_count = torch.zeros(3, dtype=torch.int32, device=dev)  # accumulator, wg counter, last count
-        self.reset_masks = torch.zeros((N + 63) // 64, dtype=torch.int64, device=dev)
+        # {count, seq} published by post_a straight into pinned host memory (gt_wait_host_seq)
+        self._done = DoneCounter(N, dev)
+        self.reset_count, self.reset_masks = self._done.reset_count, self._done.reset_masks
         # GT_ANYMAL_RESET_SCRATCH_WORDS: re-armed counter (16 words) + per-wave episode partial sums
         self.reset_scratch = torch.zeros(16 + (len(self.TERMS) + 1) * ((N + 63) // 64), dtype=torch.float32,
                                          device=dev)
-        # {count, seq} published by post_a straight into pinned host memory (gt_wait_host_seq)
-        h, d = C.c_void_p(), C.c_void_p()
-        _check(L.gt_host_alloc(8, C.byref(h), C.byref(d)), "gt_host_alloc")
-        self._host_words, self._host_words_dev = h.value, d.value
-        self._seq = 0
-        self._count_out = C.c_int32(0)
         # reference draws (reset offsets/commands, obs noise) evaluated inside the kernels from the
         # device generator's Philox stream (bit-identical to torch.rand); False: torch draws buffers
         self.inkernel_rng = True
@@ -660,11 +648,6 @@ class AnymalTailKernels:
             v.term_link_idx[k] = int(i)
         return v
 
-    def __del__(self):
-        if getattr(self, "_host_words", None) and _lib is not None:
-            _lib.gt_host_free(self._host_words)
-            self._host_words = None
-
     # task attributes whose storage the kernels use; rebuilt only when one of them is rebound
     _STABLE = ("root_states", "contact_forces", "dof_state", "last_actions", "last_dof_vel", "commands",
                "feet_air_time", "progress_buf", "randomize_buf", "rew_buf", "base_lin_vel", "base_ang_vel",
@@ -687,9 +670,7 @@ class AnymalTailKernels:
             b.reset_buf = self.reset_bool.data_ptr()
             b.episode_sums = self.sums.data_ptr()
             b.noise_scale = self.noise_scale.data_ptr()
-            b.reset_count = self.reset_count.data_ptr()
-            b.host_count = self._host_words_dev
-            b.reset_masks = self.reset_masks.data_ptr()
+            self._done.fill(b)
             self._b, self._bound = b, cur
         b.torques = t.torques.data_ptr()
         b.actions = t.actions.data_ptr()
@@ -712,8 +693,7 @@ class AnymalTailKernels:
         if not t.actions.is_contiguous():
             t.actions = t.actions.contiguous()
         b = self._buffers()
-        self._seq = (self._seq + 1) & 0x7FFFFFFF
-        b.seq = self._seq
+        b.seq = self._done.next_seq()
         _check(lib().gt_anymal_post_physics_a(self.p, b, self._stream()), "gt_anymal_post_physics_a")
         t.reset_buf = self.reset_bool  # check_termination makes reset_buf a bool tensor (anymal_terrain.py:295)
 
@@ -746,8 +726,7 @@ class AnymalTailKernels:
         b = self._buffers()
         if any(x % 16 for x in (b.torques, b.actions, b.last_actions, b.last_dof_vel, b.dof_state)):
             return None
-        self._seq = (self._seq + 1) & 0x7FFFFFFF
-        b.seq = self._seq
+        b.seq = self._done.next_seq()
         return self.p, b
 
     def after_fused_tail(self):
@@ -757,6 +736,22 @@ class AnymalTailKernels:
     _tail_ok = None
     _tail_sim_ok = None
     _ids_buf = None
+
+    def _reset_draws(self):
+        """Builds the resets' GtAnymalResetDraws: its affine maps are fixed per task."""
+        t = self.task
+        d = self._draws = GtAnymalResetDraws()
+        for name, (lo, hi) in (("pos", (0.5, 1.5)), ("vel", (-0.1, 0.1)), ("cmd_x", t.command_x_range),
+                               ("cmd_y", t.command_y_range), ("cmd_h", t.command_yaw_range)):
+            setattr(d, name + "_range", float(hi - lo))
+            setattr(d, name + "_lower", float(lo))
+        return d
+
+    def _ids(self):
+        """Allocates the persistent int32 [num_envs] buffer the resets write the flagged env ids into."""
+        t = self.task
+        self._ids_buf = torch.empty(t.num_envs, dtype=torch.int32, device=t.device)
+        return self._ids_buf
 
     def post_ab_applies(self) -> bool:
         """post_a and the (optimistic) observations can be one launch (gt_anymal_post_physics_ab): AnymalTerrain on
@@ -784,8 +779,7 @@ class AnymalTailKernels:
             self.post_a()
             self.observe()
             return
-        self._seq = (self._seq + 1) & 0x7FFFFFFF
-        b.seq = self._seq
+        b.seq = self._done.next_seq()
         plan = self.planner.plan(t.obs_buf.numel()) if t.add_noise else None
         obs = torch.empty_like(t.obs_buf)
         time_outs = torch.empty(t.num_envs, dtype=torch.bool, device=t.device)
@@ -806,9 +800,7 @@ class AnymalTailKernels:
     WAIT_TIMEOUT_MS = 60000
 
     def wait_reset_count(self) -> int:
-        _check(lib().gt_wait_host_seq(self._host_words, self._seq, self.WAIT_TIMEOUT_MS, C.byref(self._count_out)),
-               "gt_wait_host_seq")
-        self.last_reset_count = int(self._count_out.value)
+        self.last_reset_count = self._done.wait(self.WAIT_TIMEOUT_MS)
         return self.last_reset_count
 
     def rng_snapshot(self):
@@ -883,12 +875,8 @@ class AnymalTailKernels:
         tr = self._terrain_reset() if t.custom_origins else None
         h = self._h
         d = self._draws
-        if d is None:  # the affine maps are fixed per task
-            d = self._draws = GtAnymalResetDraws()
-            for name, (lo, hi) in (("pos", (0.5, 1.5)), ("vel", (-0.1, 0.1)), ("cmd_x", t.command_x_range),
-                                   ("cmd_y", t.command_y_range), ("cmd_h", t.command_yaw_range)):
-                setattr(d, name + "_range", float(hi - lo))
-                setattr(d, name + "_lower", float(lo))
+        if d is None:
+            d = self._reset_draws()
         # draw order (anymal_terrain.py:385-398, useful_hound.py:571-605): dof offsets, dof velocities,
         # [trimesh: root x, y], [UsefulHound: arm reset noise (k, 6)], command x, y, heading
         if self.inkernel_rng:
@@ -922,8 +910,8 @@ class AnymalTailKernels:
         # the flagged env ids: a prefix of one persistent buffer (stream order keeps the previous reset's readers
         # ahead of this write); extras["episode"] gets a fresh buffer per reset, as the reference's torch.mean
         ids_buf = self._ids_buf
-        if ids_buf is None or ids_buf.numel() < t.num_envs:
-            ids_buf = self._ids_buf = torch.empty(t.num_envs, dtype=torch.int32, device=dev)
+        if ids_buf is None:
+            ids_buf = self._ids()
         ids = ids_buf[:k]
         ep = torch.empty(len(self.TERMS) + 1, dtype=torch.float32, device=dev)
         _check(lib().gt_anymal_reset_flagged(self.p, self._buffers(check=False), k, d, tr, ids.data_ptr(), ep.data_ptr(),
@@ -974,8 +962,9 @@ class AnymalTailKernels:
         # the reset draws start where the optimistic noise did (the rolled-back offset); with no reset the generator
         # stays after the optimistic draws
         args, off, outs = self._ro_prepare(None if snap is None else snap[0])
-        cnt = self._count_out
-        rc = lib().gt_anymal_wait_reset_observe(self._host_words, self._seq, self.WAIT_TIMEOUT_MS, C.byref(cnt),
+        done = self._done
+        cnt = done.out
+        rc = lib().gt_anymal_wait_reset_observe(done.host_words, done.seq, self.WAIT_TIMEOUT_MS, C.byref(cnt),
                                                 self.p, *args)
         _check(rc, "gt_anymal_wait_reset_observe")
         k = self.last_reset_count = int(cnt.value)
@@ -987,14 +976,10 @@ class AnymalTailKernels:
         t = self.task
         d = self._draws
         if d is None:
-            d = self._draws = GtAnymalResetDraws()
-            for name, (lo, hi) in (("pos", (0.5, 1.5)), ("vel", (-0.1, 0.1)), ("cmd_x", t.command_x_range),
-                                   ("cmd_y", t.command_y_range), ("cmd_h", t.command_yaw_range)):
-                setattr(d, name + "_range", float(hi - lo))
-                setattr(d, name + "_lower", float(lo))
+            d = self._reset_draws()
         ids_buf = self._ids_buf
-        if ids_buf is None or ids_buf.numel() < t.num_envs:
-            ids_buf = self._ids_buf = torch.empty(t.num_envs, dtype=torch.int32, device=t.device)
+        if ids_buf is None:
+            ids_buf = self._ids()
         # fresh outputs (extras["episode"], the observations, time_outs): allocated after the previous reset's call,
         # off the host path between the count and this one
         nxt = self._ro_next
