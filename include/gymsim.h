@@ -295,6 +295,12 @@ int gs_sim_bind_dof_properties_env(gs_sim *sim, const float *table, int any_driv
  * by a joint.  enable = 1 turns the model's pairs on (every actor of the sim must agree). */
 int gs_sim_set_self_collision(gs_sim *sim, int enable);
 
+/* AssetOptions.disable_gravity of the sim's one asset (additive entry point, no ABI bump): disable = 1 makes the
+ * gravity of every kernel form -- one env per lane, lane team, runtime-sized kernel, host backend, and the DOF force
+ * tensor's pass with them -- zero; gs_sim_params.gravity keeps its value and 0 puts it back in force.  Valid from
+ * gs_sim_create on; refused after gs_sim_prepare. */
+int gs_sim_set_disable_gravity(gs_sim *sim, int disable);
+
 /* Physics kernel selected by gs_sim_set_model: 1 one env per lane, 2 lane team, 3 host backend, 4 the
  * runtime-sized kernel (ABI 8: a topology with no compiled kernel -- any tree of revolute / prismatic joints with
  * plane contacts of sphere / capsule / cylinder / box candidates and convex-hull manifolds, joint limits, drives,

@@ -393,6 +393,71 @@ typedef struct gt_flat_reset_args {
 int gt_flat_reset_flagged(const gt_flat_params *p, const gt_flat_buffers *b, int k, const gt_flat_reset_args *r,
                           void *stream);
 
+/* ---- Houndarm (tasks/hound_arm.py): OSC reach on a fixed-base 6-DoF arm, fused; additive entry points, no ABI bump.
+ * One lane per env, 64-lane workgroups.
+ *
+ * gt_arm_control: pre_physics_step + _compute_osc_torques (hound_arm.py:462-523) for every env,
+ *   dpose = actions[e] * cmd_limit / action_scale,
+ *   M = mass_matrix[e] (6x6), J = jacobian[e][jac_row][:][0:6] (nv = 6), v_eef = rigid_body[e*nl+eef_link][7:13],
+ *   u = the operational-space controller of gt_hound_control (the same float64 code, csrc/gt_osc6.h) with the
+ *       null-space term about dof_default, clamped to +-effort_limit
+ *   -> torques [N][6] and the effort tensor the sim reads (row stride effort_stride floats), the same values.
+ * actions [N][6], dof_state [N*6][2], mass_matrix [N][6][6], jacobian [N][nl][6][6], rigid_body [N*nl][13]. */
+typedef struct gt_arm_params {
+    int32_t num_envs, num_links, jac_row, eef_link, effort_stride;
+    int32_t max_episode_length;
+    float action_scale;
+    float kp[6], kd[6], kp_null[6], kd_null[6], cmd_limit[6], dof_default[6], effort_limit[6];
+    float dof_lower[6], dof_upper[6];
+    float dof_noise2;                  /* float(houndarmDofNoise * 2.0) */
+    float r_dist, r_vel;               /* distRewardScale, velRewardScale */
+} gt_arm_params;
+
+int gt_arm_control(const gt_arm_params *p, const float *actions, const float *dof_state, const float *mass_matrix,
+                   const float *jacobian, const float *rigid_body, float *torques, float *effort, void *stream);
+
+/* gt_arm_post_physics: compute_observations + compute_houndarm_reward (hound_arm.py:386-395, 551-567) after the
+ * step's reset and refreshes.  Per env, with the end-effector row eef = rigid_body[e*nl+eef_link]:
+ *   obs_buf [N][10] = eef position (3) | eef quaternion (4) | commands (3)
+ *   d = |eef_pos - commands|,  v = |eef velocity| over all six components
+ *   rew_buf [N]     = max(0, (1 - tanh(10 d)) r_dist + (1 - tanh(10 v)) [d < 0.02] r_vel)
+ *   reset_buf [N]   = int64, 1 on progress_buf >= max_episode_length - 1, else kept
+ * and the ballots of reset_buf != 0 go to reset_masks, their count {count, seq} to host_count, as
+ * gt_flat_post_physics publishes them. */
+typedef struct gt_arm_buffers {
+    const float *rigid_body, *commands;
+    float *obs_buf, *rew_buf;
+    int64_t *reset_buf;
+    const int64_t *progress_buf;
+    int32_t *reset_count;        /* [3] device, zero-initialised accumulator (re-armed by the kernel) */
+    int32_t *host_count;         /* [2] host-mapped {count, seq} or NULL */
+    int32_t seq;
+    uint64_t *reset_masks;       /* [ceil(N/64)] the done mask's per-wave ballots (gt_arm_reset_flagged) */
+} gt_arm_buffers;
+
+int gt_arm_post_physics(const gt_arm_params *p, const gt_arm_buffers *b, void *stream);
+
+/* reset_idx (hound_arm.py:397-459), fused, for the k envs the previous gt_arm_post_physics flagged (its reset_masks
+ * ballots; env ids ascending = torch's nonzero order).  Four consecutive torch.rand plans in the reference's order --
+ * command x, y, z (k values each, range * u + lower) and torch.rand((k, 6)) -- evaluated in-kernel, bit-identically
+ * to torch's Philox:
+ *   q[e]  = clamp(dof_default + dof_noise2 * (u - 0.5), dof_lower, dof_upper), qd[e] = 0
+ *   pos_control[e] = q[e], effort_control[e] = 0 (rows of effort_stride floats)
+ *   progress_buf[e] = 0, reset_buf[e] = 0, env_ids_out[rank] = e
+ * The caller then applies the reference's indexed sets (targets, efforts, dof state) with env_ids_out. */
+typedef struct gt_arm_reset_args {
+    gt_torch_rand_plan plan[4];        /* command x, y, z, dof noise */
+    float range[3], lower[3];          /* the commands' torch_rand_float maps */
+    float *dof_state;                  /* [N*6][2] the task's dof tensor */
+    float *commands;                   /* [N][3] */
+    float *pos_control, *effort_control; /* [N][effort_stride] */
+    int64_t *progress_buf;             /* [N] */
+    int32_t *env_ids_out;              /* [>= k] */
+} gt_arm_reset_args;
+
+int gt_arm_reset_flagged(const gt_arm_params *p, const gt_arm_buffers *b, int k, const gt_arm_reset_args *r,
+                         void *stream);
+
 /* out[plan.numel] = torch.rand(plan.numel) for the given plan (checks torch_philox.h against torch) */
 int gt_torch_rand(const gt_torch_rand_plan *plan, float *out, void *stream);
 

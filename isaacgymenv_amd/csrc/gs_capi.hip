@@ -79,6 +79,7 @@ struct gs_sim {
   gs_sim_params params{};
   DevParams dp{};
   bool has_ground = false;
+  bool disable_gravity = false;  // gs_sim_set_disable_gravity: the asset's AssetOptions.disable_gravity
   float ground_mu = 1.f;
   const TopoEntry* topo = nullptr;
   const TeamEntry* team = nullptr;  // the topology's lane-team kernels (gs_team.hip), null if it has none
@@ -122,6 +123,12 @@ struct gs_sim {
   const DevModel* model() const { return host ? &h_model : d_model; }
   const DevLinks* links() const { return host ? &h_links : d_links; }
 };
+
+// The gravity every kernel form sees (DevParams::g; the bias pass of the lane, team, runtime-sized and host forms and
+// the DOF-force pass that reuses its result): the sim parameter, or zero with the asset's gravity switched off
+static void fill_gravity(gs_sim* s) {
+  for (int k = 0; k < 3; ++k) s->dp.g[k] = s->disable_gravity ? 0.f : (float)s->params.gravity[k];
+}
 
 // The launch pointers of a kernel form (under variant 4, s->topo is the runtime-sized kernel's own entry)
 static void set_variant(gs_sim* s, int variant) {
@@ -171,7 +178,7 @@ gs_sim* gs_sim_create(int device, const gs_sim_params* p) {
   const int sub = p->substeps > 0 ? p->substeps : 1;
   s->dp.h = (float)(p->dt / sub);
   s->dp.substeps = sub;
-  for (int k = 0; k < 3; ++k) s->dp.g[k] = (float)p->gravity[k];
+  fill_gravity(s);
   s->dp.pos_iters = p->num_position_iterations;
   s->dp.vel_iters = p->num_velocity_iterations;
   s->dp.contact_offset = (float)p->contact_offset;
@@ -641,6 +648,14 @@ int gs_sim_set_self_collision(gs_sim* s, int enable) {
   if (enable && s->h_model.np > 0 && s->topo->npk <= 0)
     return fail("gs_sim_set_self_collision: the compiled topology has no self-contact pool");
   s->dp.self_collide = enable && s->h_model.np > 0;
+  return 0;
+}
+
+int gs_sim_set_disable_gravity(gs_sim* s, int disable) {
+  if (!s) return fail("gs_sim_set_disable_gravity: null sim");
+  if (s->state) return fail("gs_sim_set_disable_gravity: call before gs_sim_prepare");
+  s->disable_gravity = disable != 0;
+  fill_gravity(s);
   return 0;
 }
 

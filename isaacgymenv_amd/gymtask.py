@@ -154,6 +154,26 @@ class GtFlatResetArgs(C.Structure):
         (n, C.c_void_p) for n in ("dof_state", "commands", "progress_buf", "env_ids_out")]
 
 
+class GtArmParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_envs", "num_links", "jac_row", "eef_link", "effort_stride",
+                                         "max_episode_length")] + [("action_scale", C.c_float)] + [
+        (n, C.c_float * 6) for n in ("kp", "kd", "kp_null", "kd_null", "cmd_limit", "dof_default", "effort_limit",
+                                     "dof_lower", "dof_upper")] + [
+        (n, C.c_float) for n in ("dof_noise2", "r_dist", "r_vel")]
+
+
+class GtArmBuffers(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("rigid_body", "commands", "obs_buf", "rew_buf", "reset_buf", "progress_buf",
+                                          "reset_count", "host_count")] + [("seq", C.c_int32),
+                                                                           ("reset_masks", C.c_void_p)]
+
+
+class GtArmResetArgs(C.Structure):
+    _fields_ = [("plan", GtTorchRandPlan * 4), ("range", C.c_float * 3), ("lower", C.c_float * 3)] + [
+        (n, C.c_void_p) for n in ("dof_state", "commands", "pos_control", "effort_control", "progress_buf",
+                                  "env_ids_out")]
+
+
 _lib = None
 
 
@@ -272,6 +292,10 @@ def _argtypes():
             "gt_flat_post_physics": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), vp],
             "gt_flat_reset_flagged": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), i,
                                       C.POINTER(GtFlatResetArgs), vp],
+            "gt_arm_control": [C.POINTER(GtArmParams), vp, vp, vp, vp, vp, vp, vp, vp],
+            "gt_arm_post_physics": [C.POINTER(GtArmParams), C.POINTER(GtArmBuffers), vp],
+            "gt_arm_reset_flagged": [C.POINTER(GtArmParams), C.POINTER(GtArmBuffers), i,
+                                     C.POINTER(GtArmResetArgs), vp],
             "gt_anymal_reset_observe": [P, B, i, C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
                                         C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp, vp,
                                         vp, vp],
@@ -484,6 +508,88 @@ class FlatTailKernel(_FusedTail):
         return (("root_states", t.root_states), ("dof_state", t.dof_state), ("contact_forces", t.contact_forces),
                 ("torques", t.torques), ("actions", t.actions), ("commands", t.commands),
                 ("default_dof_pos", t.default_dof_pos), ("gravity_vec", t.gravity_vec), ("obs_buf", t.obs_buf),
+                ("rew_buf", t.rew_buf), ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf))
+
+
+class ArmKernels(_FusedTail):
+    """gt_arm_control / gt_arm_post_physics / gt_arm_reset_flagged bound to one Houndarm env (tasks/hound_arm.py, GPU
+    pipeline): the operational-space controller in one launch, observations + reward + time-out mask in one launch
+    with the done count published to pinned host memory, and reset_idx of the flagged envs in one launch plus the
+    reference's three indexed sets."""
+
+    POST, BUFFERS = "gt_arm_post_physics", GtArmBuffers
+
+    def __init__(self, env):
+        t = env
+        p = GtArmParams()
+        p.num_envs, p.num_links = t.num_envs, int(t.rigid_body_state.shape[1])
+        p.jac_row, p.eef_link = int(t.hand_joint_index), int(t.eef_index)
+        p.effort_stride = int(t.effort_control.stride(0))
+        p.max_episode_length = int(t.max_episode_length)
+        p.action_scale = float(t.action_scale)
+        for name, ten in (("kp", t.kp), ("kd", t.kd), ("kp_null", t.kp_null), ("kd_null", t.kd_null),
+                          ("cmd_limit", t.cmd_limit), ("dof_default", t.default_dof_pos),
+                          ("effort_limit", t.effort_limits), ("dof_lower", t.dof_lower_limits),
+                          ("dof_upper", t.dof_upper_limits)):
+            getattr(p, name)[:] = [float(v) for v in ten.detach().cpu().reshape(-1)[:6]]
+        p.dof_noise2 = float(t.dof_noise * 2.0)
+        p.r_dist, p.r_vel = float(t.reward_settings["r_dist_scale"]), float(t.reward_settings["r_vel_scale"])
+        super().__init__(env, p)
+        self.jacobian, self.mass_matrix = t.jacobian_full, t.mass_matrix
+        for ten in (t.dof_state, self.mass_matrix, t.rigid_body_state, t.effort_control, t.pos_control):
+            assert ten.is_contiguous() and ten.dtype == torch.float32 and ten.is_cuda
+        # the fixed-base Jacobian tensor is a view of the sim's [N][links][6][6] without the welded root's row: the
+        # kernel walks the sim's rows from the view's first element, so the view's row r is its row r
+        j = self.jacobian
+        assert j.dtype == torch.float32 and j.is_cuda and j.shape[2:] == (6, 6) and p.jac_row < j.shape[1]
+        assert j.stride() == (p.num_links * 36, 36, 6, 1) and j.shape[1] <= p.num_links
+        assert self.mass_matrix.shape[1:] == (6, 6) and t.pos_control.stride(0) == p.effort_stride
+
+    def control(self, actions, effort):
+        """hound_arm.py:462-523 for every env: the clamped OSC torques into the task's effort_control and into
+        ``effort`` (the tensor the sim reads its actuation forces from, rows of effort_stride floats)."""
+        t = self.env
+        assert actions.is_contiguous() and actions.dtype == torch.float32 and actions.shape == (t.num_envs, 6)
+        assert effort.is_contiguous() and effort.numel() == t.effort_control.numel()
+        _check(lib().gt_arm_control(C.byref(self.p), actions.data_ptr(), t.dof_state.data_ptr(),
+                                    self.mass_matrix.data_ptr(), self.jacobian.data_ptr(),
+                                    t.rigid_body_state.data_ptr(), t.effort_control.data_ptr(), effort.data_ptr(),
+                                    C.c_void_p(raw_stream(actions.device))), "gt_arm_control")
+
+    def __call__(self):
+        self._done.next_seq()
+        _check(self._post(C.byref(self.p), C.byref(self._buffers()),
+                          C.c_void_p(raw_stream(self.env.dof_state.device))), self.POST)
+        self._launched = True
+
+    def reset_flagged(self, k: int):
+        """hound_arm.py:397-459 reset_idx for the k envs the previous launch flagged: the four torch.rand draws
+        evaluated in-kernel from the device generator (advanced exactly as the four calls would), commands, dof state,
+        controls and counters, then the reference's three indexed sets.  Returns the env ids (int32 [k])."""
+        from .isaacgym import gymtorch
+        t = self.env
+        r = GtArmResetArgs()
+        for i, plan in enumerate(self.planner.plan_many((k, k, k, k * 6))):
+            r.plan[i] = plan
+        # torch_rand_float(lower, upper): (upper - lower) * rand + lower, the range a Python double
+        for i, (lo, hi) in enumerate((t.command_x_range, t.command_y_range, t.command_z_range)):
+            r.range[i], r.lower[i] = hi - lo, lo
+        r.dof_state, r.commands = t.dof_state.data_ptr(), t.commands.data_ptr()
+        r.pos_control, r.effort_control = t.pos_control.data_ptr(), t.effort_control.data_ptr()
+        r.progress_buf, r.env_ids_out = t.progress_buf.data_ptr(), self.env_ids.data_ptr()
+        _check(lib().gt_arm_reset_flagged(C.byref(self.p), C.byref(self._buffers()), k, C.byref(r),
+                                          C.c_void_p(raw_stream(t.dof_state.device))), "gt_arm_reset_flagged")
+        ids = self.env_ids[:k]
+        t.gym.set_dof_position_target_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.pos_control),
+                                                     gymtorch.unwrap_tensor(ids), k)
+        t.gym.set_dof_actuation_force_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.effort_control),
+                                                     gymtorch.unwrap_tensor(ids), k)
+        t.gym.set_dof_state_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.dof_state), gymtorch.unwrap_tensor(ids), k)
+        return ids
+
+    def tensors(self):
+        t = self.env
+        return (("rigid_body", t.rigid_body_state), ("commands", t.commands), ("obs_buf", t.obs_buf),
                 ("rew_buf", t.rew_buf), ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf))
 
 

@@ -99,7 +99,8 @@ def convex_hull_vertices(vertices: np.ndarray) -> np.ndarray:
 
 def _mesh_file(urdf_dir: str, filename: str) -> Optional[str]:
     name = filename[len("package://"):] if filename.startswith("package://") else filename
-    for base in (urdf_dir, os.path.dirname(urdf_dir)):
+    # (the third base: package://<pkg>/meshes/x.stl named from <pkg>/urdf/, the ROS package layout)
+    for base in (urdf_dir, os.path.dirname(urdf_dir), os.path.dirname(os.path.dirname(urdf_dir))):
         p = os.path.join(base, name)
         if os.path.isfile(p):
             return p
@@ -758,6 +759,11 @@ def load_raw(root: str, filename: str) -> RawModel:
     if os.path.isfile(path) and path.endswith(".xml"):
         from . import _mjcf
         return _mjcf.parse_mjcf(path)
+    if os.path.isfile(path) and path.endswith(".model.json"):
+        # a packed model given as the asset file itself (tools/pack_assets.py's form; the Houndarm arm, whose model
+        # is not shipped in PACKED_DIR)
+        with open(path) as f:
+            return RawModel.from_json(json.load(f))
     # (of the whole path: Hound_terrain.py:212-216 passes the directory as the root and "Hound.urdf" as the file)
     key2 = "/".join(path.replace(os.sep, "/").split("/")[-2:])
     for key in (key2, base):

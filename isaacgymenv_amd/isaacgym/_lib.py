@@ -100,6 +100,7 @@ def lib():
             "gs_sim_pd_tail_supported": (i, [vp]),
             "gs_sim_set_root_and_dof": (i, [vp, vp, vp, vp, i, vp]),
             "gs_sim_set_self_collision": (i, [vp, i]),
+            "gs_sim_set_disable_gravity": (i, [vp, i]),
             "gs_sim_refresh_force_sensor": (i, [vp, vp, vp]),
             "gs_sim_bind_dof_force": (i, [vp, vp]),
             "gs_sim_refresh_dof_force": (i, [vp, vp, vp]),
@@ -132,6 +133,7 @@ EXPORTED_SYMBOLS = [
     "gs_sim_add_triangle_mesh", "gs_debug_terrain_query", "gs_sim_refresh_rigid_body", "gs_sim_refresh_jacobian",
     "gs_sim_refresh_mass_matrix", "gs_sim_set_dof_drives", "gs_sim_bind_dof_targets", "gs_sim_set_self_collision",
     "gs_debug_self_contacts", "gs_debug_team_form", "gs_debug_team_sweeps", "gs_sim_bind_dof_properties_env", "gs_sim_pd_tail_supported", "gs_sim_set_root_and_dof",
+    "gs_sim_set_disable_gravity",
 ]
 
 

@@ -321,6 +321,7 @@ class Sim:
         self.ground: Optional[PlaneParams] = None
         self.mesh = None
         self.prepared = False
+        self.warned_fixed_self_collision = False
         self.drives_dirty = False
         self.handle = None
         self._pd_args, self._pd_key = None, None  # Gym.amd_pd_decimation_step's cached argument struct
@@ -386,6 +387,9 @@ class Sim:
             _lib.check(L.gs_sim_add_triangle_mesh(self.handle, v.ctypes.data, v.size // 3, t.ctypes.data, t.size // 3,
                                                   tpa, smu, dmu, rest), "gs_sim_add_triangle_mesh")
         _lib.check(L.gs_sim_set_model(self.handle, desc), "gs_sim_set_model")
+        # AssetOptions.disable_gravity: one asset per sim, so the asset's flag is the sim's
+        self.disable_gravity = bool(self.asset.options.disable_gravity)
+        _lib.check(L.gs_sim_set_disable_gravity(self.handle, int(self.disable_gravity)), "gs_sim_set_disable_gravity")
         # collision filter 0: Isaac Gym collides the actor's own shapes
         filters = {a.filter == 0 for e in self.envs for a in e.actors}
         if len(filters) > 1:
@@ -836,6 +840,14 @@ class Gym:
             owner.asset = asset
         elif owner.asset is not asset:
             raise NotImplementedError("one asset type per sim (DESIGN.md section 6)")
+        if filter == 0 and asset.art.fixed_base and not getattr(owner, "warned_fixed_self_collision", False):
+            # (once per sim: a task creates one such actor per env)
+            pairs = asset.art.self_collision_pairs()
+            if pairs:
+                owner.warned_fixed_self_collision = True
+                warnings.warn(f"{asset.art.name}: self-collision (collision filter 0) of a fixed-base articulation is "
+                              f"not simulated; {len(pairs)} shape pairs on links that could collide are dropped "
+                              f"(DESIGN.md section 6)", PhysicsDeviationWarning, stacklevel=2)
         return len(env.actors) - 1
 
     def get_actor_count(self, env: Env) -> int:
@@ -843,6 +855,9 @@ class Gym:
 
     def get_sim_actor_count(self, sim: Sim) -> int:
         return sum(len(e.actors) for e in sim.envs)
+
+    def get_sim_dof_count(self, sim: Sim) -> int:
+        return sum(a.asset.art.num_dofs for e in sim.envs for a in e.actors)
 
     def get_actor_dof_properties(self, env: Env, actor: int):
         return env.actors[actor].dof_props.copy()

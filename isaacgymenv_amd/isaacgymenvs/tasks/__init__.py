@@ -3,6 +3,7 @@ from .ant import Ant
 from .anymal import Anymal, Hound
 from .anymal_terrain import AnymalTerrain
 from .cartpole import Cartpole
+from .hound_arm import Houndarm
 from .hound_terrain import HoundTerrain
 from .useful_hound import UsefulHound
 
@@ -13,5 +14,6 @@ isaacgym_task_map = {
     "Cartpole": Cartpole,
     "Hound": Hound,
     "HoundTerrain": HoundTerrain,
+    "Houndarm": Houndarm,
     "UsefulHound": UsefulHound,
 }

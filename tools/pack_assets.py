@@ -27,16 +27,23 @@ SOURCES = {
     # the fork's own quadruped (hound.py:168-183): no compiled topology, the runtime-sized kernel runs it
     "hound_new.model.json": "urdf/Hound_new/Hound.urdf",
 }
+# models that are test fixtures only (tests/golden/), not shipped with the package: the Houndarm task's fixed-base
+# Open Manipulator P (hound_arm.py:201), which a user loads from the reference's own URDF
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+GOLDEN_SOURCES = {
+    "open_manipulator_p.model.json": "urdf/open_manipulator_p_gazebo/urdf/open_manipulator_p.urdf",
+}
 
 
 def main():
     os.makedirs(PACKED_DIR, exist_ok=True)
-    for out, src in SOURCES.items():
-        path = os.path.join(REF, src)
-        raw = parse_mjcf(path) if src.endswith(".xml") else parse_urdf(path)
-        with open(os.path.join(PACKED_DIR, out), "w") as f:
-            json.dump(raw.to_json(), f, indent=1)
-        print("packed", src, "->", out)
+    for folder, sources in ((PACKED_DIR, SOURCES), (GOLDEN_DIR, GOLDEN_SOURCES)):
+        for out, src in sources.items():
+            path = os.path.join(REF, src)
+            raw = parse_mjcf(path) if src.endswith(".xml") else parse_urdf(path)
+            with open(os.path.join(folder, out), "w") as f:
+                json.dump(raw.to_json(), f, indent=1)
+            print("packed", src, "->", os.path.join(os.path.relpath(folder, ROOT), out))
 
 
 if __name__ == "__main__":
