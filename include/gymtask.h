@@ -458,6 +458,47 @@ typedef struct gt_arm_reset_args {
 int gt_arm_reset_flagged(const gt_arm_params *p, const gt_arm_buffers *b, int k, const gt_arm_reset_args *r,
                          void *stream);
 
+/* ---- Manipulator (tasks/manipulator.py): OSC reach on a fixed-base 7-DoF arm; additive entry points, no ABI bump.
+ * The tail is gt_arm_post_physics (it reads no per-dof array).
+ *
+ * gt_osc_control: gt_arm_control's computation for nd = 6 or 7 dofs with one env spread over a team of 8 lanes, 8 envs
+ * per 64-lane workgroup (csrc/gt_manip.hip).  The task space stays 6 wide:
+ *   dpose = actions[e] * cmd_limit / action_scale,
+ *   M = mass_matrix[e] (nd x nd), J = jacobian[e][jac_row] (6 x nd), v_eef = rigid_body[e*nl+eef_link][7:13],
+ *   u = J^T M_eef (kp dpose - kd v_eef) + (1 - J^T M_eef J M^-1) M u_null,  M_eef = (J M^-1 J^T)^-1,
+ *   u_null = -kd_null qd + kp_null ((dof_default - q + pi) mod 2 pi - pi),  clamped to +-effort_limit
+ *   -> torques [N][nd] and the effort tensor the sim reads (row stride effort_stride floats), the same values.
+ * In float64, the operations and their order those of csrc/gt_osc6.h: at nd = 6 the bits are gt_arm_control's.
+ * actions [N][6], dof_state [N*nd][2], mass_matrix [N][nd][nd], jacobian [N][nl][6][nd], rigid_body [N*nl][13]. */
+typedef struct gt_manip_params {
+    int32_t num_envs, nd, num_links, jac_row, eef_link, effort_stride;
+    float action_scale;
+    float kp[6], kd[6], cmd_limit[6];  /* task space */
+    float kp_null[8], kd_null[8], dof_default[8], effort_limit[8], dof_lower[8], dof_upper[8]; /* per dof, nd used */
+    float dof_noise2;                  /* float(frankaDofNoise * 2.0) */
+} gt_manip_params;
+
+int gt_osc_control(const gt_manip_params *p, const float *actions, const float *dof_state, const float *mass_matrix,
+                   const float *jacobian, const float *rigid_body, float *torques, float *effort, void *stream);
+
+/* reset_idx (manipulator.py:390-452), fused, for the k envs the previous gt_arm_post_physics flagged: as
+ * gt_arm_reset_flagged for nd = 7, with plans of k, k, k, 7k and the reference's rule that the last two joints are set
+ * to dof_default exactly after the clamp (their draws are consumed):
+ *   q[e][j] = j < 5 ? clamp(dof_default + dof_noise2 * (u - 0.5), dof_lower, dof_upper) : dof_default[j], qd[e] = 0
+ *   pos_control[e] = q[e], effort_control[e] = 0, progress_buf[e] = 0, reset_buf[e] = 0, env_ids_out[rank] = e */
+typedef struct gt_manip_reset_args {
+    gt_torch_rand_plan plan[4];        /* command x, y, z, dof noise */
+    float range[3], lower[3];          /* the commands' torch_rand_float maps */
+    float *dof_state;                  /* [N*7][2] the task's dof tensor */
+    float *commands;                   /* [N][3] */
+    float *pos_control, *effort_control; /* [N][effort_stride] */
+    int64_t *progress_buf;             /* [N] */
+    int32_t *env_ids_out;              /* [>= k] */
+} gt_manip_reset_args;
+
+int gt_manip_reset_flagged(const gt_manip_params *p, const gt_arm_buffers *b, int k, const gt_manip_reset_args *r,
+                           void *stream);
+
 /* out[plan.numel] = torch.rand(plan.numel) for the given plan (checks torch_philox.h against torch) */
 int gt_torch_rand(const gt_torch_rand_plan *plan, float *out, void *stream);
 

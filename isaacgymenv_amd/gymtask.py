@@ -174,6 +174,17 @@ class GtArmResetArgs(C.Structure):
                                   "env_ids_out")]
 
 
+class GtManipParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_envs", "nd", "num_links", "jac_row", "eef_link", "effort_stride")] + [
+        ("action_scale", C.c_float)] + [(n, C.c_float * 6) for n in ("kp", "kd", "cmd_limit")] + [
+        (n, C.c_float * 8) for n in ("kp_null", "kd_null", "dof_default", "effort_limit", "dof_lower", "dof_upper")] + [
+        ("dof_noise2", C.c_float)]
+
+
+class GtManipResetArgs(C.Structure):
+    _fields_ = GtArmResetArgs._fields_
+
+
 _lib = None
 
 
@@ -296,6 +307,9 @@ def _argtypes():
             "gt_arm_post_physics": [C.POINTER(GtArmParams), C.POINTER(GtArmBuffers), vp],
             "gt_arm_reset_flagged": [C.POINTER(GtArmParams), C.POINTER(GtArmBuffers), i,
                                      C.POINTER(GtArmResetArgs), vp],
+            "gt_osc_control": [C.POINTER(GtManipParams), vp, vp, vp, vp, vp, vp, vp, vp],
+            "gt_manip_reset_flagged": [C.POINTER(GtManipParams), C.POINTER(GtArmBuffers), i,
+                                       C.POINTER(GtManipResetArgs), vp],
             "gt_anymal_reset_observe": [P, B, i, C.POINTER(GtAnymalResetDraws), vp, vp, C.c_float, vp,
                                         C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, i, vp, vp, vp,
                                         vp, vp],
@@ -540,10 +554,13 @@ class ArmKernels(_FusedTail):
             assert ten.is_contiguous() and ten.dtype == torch.float32 and ten.is_cuda
         # the fixed-base Jacobian tensor is a view of the sim's [N][links][6][6] without the welded root's row: the
         # kernel walks the sim's rows from the view's first element, so the view's row r is its row r
+        self._check_layout(p)
+
+    def _check_layout(self, p):
         j = self.jacobian
         assert j.dtype == torch.float32 and j.is_cuda and j.shape[2:] == (6, 6) and p.jac_row < j.shape[1]
         assert j.stride() == (p.num_links * 36, 36, 6, 1) and j.shape[1] <= p.num_links
-        assert self.mass_matrix.shape[1:] == (6, 6) and t.pos_control.stride(0) == p.effort_stride
+        assert self.mass_matrix.shape[1:] == (6, 6) and self.env.pos_control.stride(0) == p.effort_stride
 
     def control(self, actions, effort):
         """hound_arm.py:462-523 for every env: the clamped OSC torques into the task's effort_control and into
@@ -566,7 +583,6 @@ class ArmKernels(_FusedTail):
         """hound_arm.py:397-459 reset_idx for the k envs the previous launch flagged: the four torch.rand draws
         evaluated in-kernel from the device generator (advanced exactly as the four calls would), commands, dof state,
         controls and counters, then the reference's three indexed sets.  Returns the env ids (int32 [k])."""
-        from .isaacgym import gymtorch
         t = self.env
         r = GtArmResetArgs()
         for i, plan in enumerate(self.planner.plan_many((k, k, k, k * 6))):
@@ -579,6 +595,12 @@ class ArmKernels(_FusedTail):
         r.progress_buf, r.env_ids_out = t.progress_buf.data_ptr(), self.env_ids.data_ptr()
         _check(lib().gt_arm_reset_flagged(C.byref(self.p), C.byref(self._buffers()), k, C.byref(r),
                                           C.c_void_p(raw_stream(t.dof_state.device))), "gt_arm_reset_flagged")
+        return self._indexed_sets(k)
+
+    def _indexed_sets(self, k):
+        """The reference's three indexed sets for the k env ids the reset kernel listed; returns the ids."""
+        from .isaacgym import gymtorch
+        t = self.env
         ids = self.env_ids[:k]
         t.gym.set_dof_position_target_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.pos_control),
                                                      gymtorch.unwrap_tensor(ids), k)
@@ -591,6 +613,72 @@ class ArmKernels(_FusedTail):
         t = self.env
         return (("rigid_body", t.rigid_body_state), ("commands", t.commands), ("obs_buf", t.obs_buf),
                 ("rew_buf", t.rew_buf), ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf))
+
+
+def manip_params(nd, num_envs, num_links, jac_row, eef_link, effort_stride, action_scale, kp, kd, cmd_limit, kp_null,
+                 kd_null, dof_default, effort_limit, dof_lower, dof_upper, dof_noise2=0.0):
+    """A GtManipParams from Python numbers and per-dof sequences of nd values (the task-space ones of 6)."""
+    p = GtManipParams()
+    p.num_envs, p.nd, p.num_links, p.jac_row, p.eef_link = num_envs, nd, num_links, jac_row, eef_link
+    p.effort_stride, p.action_scale, p.dof_noise2 = effort_stride, float(action_scale), float(dof_noise2)
+    for name, vals, n in (("kp", kp, 6), ("kd", kd, 6), ("cmd_limit", cmd_limit, 6), ("kp_null", kp_null, nd),
+                          ("kd_null", kd_null, nd), ("dof_default", dof_default, nd),
+                          ("effort_limit", effort_limit, nd), ("dof_lower", dof_lower, nd),
+                          ("dof_upper", dof_upper, nd)):
+        vals = [float(v) for v in vals]
+        assert len(vals) == n, (name, len(vals), n)
+        getattr(p, name)[:n] = vals
+    return p
+
+
+class ManipulatorKernels(ArmKernels):
+    """gt_osc_control / gt_arm_post_physics / gt_manip_reset_flagged bound to one Manipulator env
+    (tasks/manipulator.py, GPU pipeline): ArmKernels with the lane-team controller and the 7-dof reset.  The tail
+    takes the arm's params (it reads no per-dof array), the other two the 7-dof params."""
+
+    ND = 7
+
+    def __init__(self, env):
+        t = env
+        super().__init__(env)
+        flat = lambda x: x.detach().cpu().reshape(-1).tolist()  # noqa: E731
+        self.mp = manip_params(self.ND, t.num_envs, self.p.num_links, self.p.jac_row, self.p.eef_link,
+                               self.p.effort_stride, t.action_scale, flat(t.kp), flat(t.kd), flat(t.cmd_limit),
+                               flat(t.kp_null), flat(t.kd_null), flat(t.default_dof_pos), flat(t.effort_limits),
+                               flat(t.dof_lower_limits), flat(t.dof_upper_limits), t.dof_noise * 2.0)
+
+    def _check_layout(self, p):
+        nd, j = self.ND, self.jacobian
+        assert j.dtype == torch.float32 and j.is_cuda and j.shape[2:] == (6, nd) and p.jac_row < j.shape[1]
+        assert j.stride() == (p.num_links * 6 * nd, 6 * nd, nd, 1) and j.shape[1] <= p.num_links
+        assert self.mass_matrix.shape[1:] == (nd, nd) and self.env.pos_control.stride(0) == p.effort_stride
+
+    def control(self, actions, effort):
+        """manipulator.py:455-516 for every env: the clamped OSC torques into the task's effort_control and into
+        ``effort`` (the tensor the sim reads its actuation forces from)."""
+        t = self.env
+        assert actions.is_contiguous() and actions.dtype == torch.float32 and actions.shape == (t.num_envs, 6)
+        assert effort.is_contiguous() and effort.numel() == t.effort_control.numel()
+        _check(lib().gt_osc_control(C.byref(self.mp), actions.data_ptr(), t.dof_state.data_ptr(),
+                                    self.mass_matrix.data_ptr(), self.jacobian.data_ptr(),
+                                    t.rigid_body_state.data_ptr(), t.effort_control.data_ptr(), effort.data_ptr(),
+                                    C.c_void_p(raw_stream(actions.device))), "gt_osc_control")
+
+    def reset_flagged(self, k: int):
+        """manipulator.py:390-452 reset_idx for the k envs the previous launch flagged, as ArmKernels.reset_flagged
+        with torch.rand((k, 7)) and the last two joints at their defaults.  Returns the env ids (int32 [k])."""
+        t = self.env
+        r = GtManipResetArgs()
+        for i, plan in enumerate(self.planner.plan_many((k, k, k, k * self.ND))):
+            r.plan[i] = plan
+        for i, (lo, hi) in enumerate((t.command_x_range, t.command_y_range, t.command_z_range)):
+            r.range[i], r.lower[i] = hi - lo, lo
+        r.dof_state, r.commands = t.dof_state.data_ptr(), t.commands.data_ptr()
+        r.pos_control, r.effort_control = t.pos_control.data_ptr(), t.effort_control.data_ptr()
+        r.progress_buf, r.env_ids_out = t.progress_buf.data_ptr(), self.env_ids.data_ptr()
+        _check(lib().gt_manip_reset_flagged(C.byref(self.mp), C.byref(self._buffers()), k, C.byref(r),
+                                            C.c_void_p(raw_stream(t.dof_state.device))), "gt_manip_reset_flagged")
+        return self._indexed_sets(k)
 
 
 class HoundControlKernel:

@@ -88,6 +88,81 @@ def read_stl(path: str) -> np.ndarray:
     return np.array(pts, dtype=np.float64)
 
 
+def read_obj(path: str) -> np.ndarray:
+    """Vertices [n, 3] of a Wavefront .obj file: its ``v x y z`` records, every other record type ignored."""
+    pts = []
+    with open(path, "r", errors="replace") as f:
+        for line in f:
+            rec = line.split()
+            if len(rec) >= 4 and rec[0] == "v":
+                pts.append([float(x) for x in rec[1:4]])
+    if not pts:
+        raise ValueError(f"{path}: no vertex records")
+    return np.array(pts, dtype=np.float64)
+
+
+MESH_READERS = {".stl": read_stl, ".obj": read_obj}
+
+
+def read_mesh_hull(path: Optional[str], scale) -> Optional[np.ndarray]:
+    """The scaled convex hull's vertices of a collision mesh file, or None when the file is missing, of no known
+    format, unreadable, or has no volume (fewer than four non-coplanar vertices)."""
+    reader = MESH_READERS.get(os.path.splitext(path)[1].lower()) if path else None
+    if reader is None:
+        return None
+    from scipy.spatial import QhullError
+    try:
+        return convex_hull_vertices(reader(path) * scale)
+    except (ValueError, QhullError):  # not a mesh of this format, or flat: qhull finds no initial simplex
+        return None
+
+
+def hull_mass_props(points: np.ndarray, rho: float):
+    """(mass, centre of mass, inertia about it) of the convex hull of ``points`` at density rho: signed-tetrahedron
+    integrals from the origin over the hull's triangulated surface."""
+    from scipy.spatial import ConvexHull
+    hull = ConvexHull(points)
+    vol, first, second = 0.0, np.zeros(3), np.zeros((3, 3))
+    canon = (np.ones((3, 3)) + np.eye(3)) / 120.0  # the second moments of the unit tetrahedron
+    for tri, eq in zip(hull.simplices, hull.equations):
+        a, b, c = points[tri]
+        if np.dot(np.cross(b - a, c - a), eq[:3]) < 0.0:  # wind the facet outward
+            b, c = c, b
+        T = np.stack([a, b, c], axis=1)
+        det = np.linalg.det(T)
+        vol += det / 6.0
+        first += det * (a + b + c) / 24.0
+        second += det * (T @ canon @ T.T)
+    com = first / vol
+    cov = second - vol * np.outer(com, com)  # integral of (x - com)(x - com)^T
+    return rho * vol, com, rho * (np.trace(cov) * np.eye(3) - cov)
+
+
+def shape_mass_props(shape: "RawShape", rho: float):
+    """(mass, centre of mass, inertia about it) of one collision shape in its link's axes, at density rho: the
+    primitives' closed forms (_mjcf.py), a convex hull's tetrahedron integrals."""
+    from . import _mjcf
+    if shape.kind == SHAPE_CONVEX:
+        m, c, I = hull_mass_props(np.asarray(shape.size, dtype=np.float64).reshape(-1, 3), rho)
+    else:
+        m, I = {SHAPE_SPHERE: lambda z: _mjcf.sphere_mass_props(z[0], rho),
+                SHAPE_CAPSULE: lambda z: _mjcf.capsule_mass_props(z[0], z[1], rho),
+                SHAPE_CYLINDER: lambda z: _mjcf.cylinder_mass_props(z[0], z[1], rho),
+                SHAPE_BOX: lambda z: _mjcf.box_mass_props(z, rho)}[shape.kind](shape.size)
+        c = np.zeros(3)
+    R = shape.pose.R
+    return m, shape.pose.apply(c), R @ I @ R.T
+
+
+def shapes_inertial(shapes, rho: float) -> "RawInertial":
+    """The inertial of a link that declares none: its collision shapes' volumes at density rho (Isaac Gym's rule,
+    AssetOptions.density), combined about their common centre of mass."""
+    m, c, I = 0.0, np.zeros(3), np.zeros((3, 3))
+    for s in shapes:
+        m, c, I = _merge_inertial(m, c, I, *shape_mass_props(s, rho))
+    return RawInertial(m, c, I)
+
+
 def convex_hull_vertices(vertices: np.ndarray) -> np.ndarray:
     """Every vertex of the mesh's convex hull (qhull through scipy), duplicates merged, in the order of
     their first occurrence in the mesh."""
@@ -188,7 +263,7 @@ class RawLink:
     name: str
     inertial: Optional[RawInertial]
     shapes: List[RawShape]
-    # collision <mesh> files the importer could not read as STL (gym.load_asset warns
+    # collision <mesh> files the importer could not read as STL or .obj (gym.load_asset warns
     # with the link names)
     dropped_meshes: List[str] = field(default_factory=list)
 
@@ -285,8 +360,26 @@ def _origin(el) -> Pose:
     return Pose(rpy_to_mat(_floats(o.get("rpy"), 3)), np.array(_floats(o.get("xyz"), 3)))
 
 
+def _urdf_root(path: str):
+    """The file's <robot> element.  A file that goes on after its root element (the reference's
+    franka_panda_manipulator.urdf closes </robot> and continues with a half-commented gripper) is read up to and
+    including its first </robot>; when that does not parse either, the original error stands."""
+    try:
+        return ET.parse(path).getroot()
+    except ET.ParseError as err:
+        with open(path, "r", errors="replace") as f:
+            text = f.read()
+        end = text.find("</robot>")
+        if end < 0:
+            raise
+        try:
+            return ET.fromstring(text[:end + len("</robot>")])
+        except ET.ParseError:
+            raise err from None
+
+
 def parse_urdf(path: str) -> RawModel:
-    root = ET.parse(path).getroot()
+    root = _urdf_root(path)
     links, order = {}, []
     for le in root.findall("link"):
         name = le.get("name")
@@ -321,16 +414,14 @@ def parse_urdf(path: str) -> RawModel:
             elif ge.find("box") is not None:
                 shapes.append(RawShape(SHAPE_BOX, op, _floats(ge.find("box").get("size"), 3)))
             elif ge.find("mesh") is not None:
-                # triangle-mesh collision geometry: its convex hull's support points (STL); a file that is
-                # missing or not STL is recorded so that gym.load_asset can name the links it affects
+                # triangle-mesh collision geometry: its convex hull's support points (STL or Wavefront .obj); a file
+                # that is missing, of another format or without volume is recorded so that gym.load_asset can name
+                # the links it affects
                 me = ge.find("mesh")
                 fn = me.get("filename", "")
                 mp = _mesh_file(os.path.dirname(os.path.abspath(path)), fn)
                 scale = np.array(_floats(me.get("scale"), 3, 1.0))
-                try:
-                    pts = convex_hull_vertices(read_stl(mp) * scale) if mp and mp.lower().endswith(".stl") else None
-                except ValueError:
-                    pts = None
+                pts = read_mesh_hull(mp, scale)
                 if pts is None:
                     dropped.append(fn)
                 else:
@@ -640,6 +731,7 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
     keep_links = not collapse and any(j.kind == JOINT_FIXED for j in raw.joints)
     weld = collapse or keep_links
     member_of: Dict[str, tuple] = {}
+    derived: Dict[str, RawInertial] = {}
     shape_link_names: List[str] = []
 
     # groups: a movable body plus everything welded to it; pose of each member in the body frame
@@ -664,10 +756,15 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
         for ln, pose in members:
             member_of[ln] = (idx, pose)
             link = raw.links[ln]
-            if link.inertial is not None and link.inertial.mass > 0:
-                mi = link.inertial.mass
-                ci = pose.apply(link.inertial.com)
-                Ii = pose.R @ link.inertial.inertia @ pose.R.T
+            inertial = link.inertial
+            # a link with collision shapes and no <inertial>: mass properties from the shapes' volumes times
+            # `density`, as Isaac Gym derives them; not for the welded root of a fixed base, which nothing moves
+            if inertial is None and link.shapes and not (joint is None and opt["fix_base_link"]):
+                inertial = derived[ln] = shapes_inertial(link.shapes, float(opt["density"]))
+            if inertial is not None and inertial.mass > 0:
+                mi = inertial.mass
+                ci = pose.apply(inertial.com)
+                Ii = pose.R @ inertial.inertia @ pose.R.T
                 m, c, I = _merge_inertial(m, c, I, mi, ci, Ii)
             for s in link.shapes:
                 kind = s.kind
@@ -694,8 +791,8 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
             j = next(jj for jj in raw.joints if jj.name == b.joint_name)
             dofs.append(Dof(j.name, bi, j.kind, j.lower, j.upper, j.has_limits, j.effort, j.velocity,
                             j.damping, j.friction, j.armature, j.motor_gear))
-    # bodies with no mass get a tiny inertia from density over their shapes' volume (Isaac Gym uses
-    # `density` for links that declare no inertial); keep M non-singular
+    # bodies with no mass (no inertial and no shapes, or a fixed base's welded root) get 1 g and a tiny inertia: keep
+    # M non-singular
     for b in bodies:
         if b.mass <= 0.0:
             b.mass = 1e-3
@@ -712,7 +809,7 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
 
         def visit(ln, parent_link):
             bi, pose = member_of[ln]
-            inert = raw.links[ln].inertial
+            inert = derived.get(ln, raw.links[ln].inertial)
             li = len(links)
             j = parent_joint.get(ln)
             links.append(Link(ln, parent_link, j.name if j is not None else "", bi, pose,

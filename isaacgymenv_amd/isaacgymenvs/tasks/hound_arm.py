@@ -52,6 +52,12 @@ ASSET_FILE = "urdf/open_manipulator_p_gazebo/urdf/open_manipulator_p.urdf"
 class Houndarm(VecTask):
     actor_name = "houndarm"
     eef_link_name, eef_joint_name = "end_link", "joint6"
+    # what a subclass on another arm overrides (tasks/manipulator.py)
+    arm_dofs = 6
+    default_pose = [0, 0, 0, 0, 0, 0]
+    dof_noise_key, asset_file_key, asset_file = "houndarmDofNoise", "assetFileNamehoundarm", ASSET_FILE
+    flip_visual_attachments = False
+    kernels_class = "ArmKernels"
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture,
                  force_render):
@@ -59,18 +65,19 @@ class Houndarm(VecTask):
         env = self.cfg["env"]
         self.max_episode_length = env["episodeLength"]
         self.action_scale = env["actionScale"]
-        self.dof_noise = env["houndarmDofNoise"]
+        self.dof_noise = env[self.dof_noise_key]
         ranges = env["randomCommandPositionRanges"]
         self.command_x_range, self.command_y_range, self.command_z_range = ranges["x"], ranges["y"], ranges["z"]
         self.reward_settings = {"r_dist_scale": env["distRewardScale"], "r_vel_scale": env["velRewardScale"]}
         self.control_type = env["controlType"]
         if self.control_type == "joint_tor":
-            raise NotImplementedError("Houndarm controlType joint_tor: the reference sizes its observation to 26 and "
-                                      "writes 10, so it does not run there either; use osc")
+            raise NotImplementedError(f"{type(self).__name__} controlType joint_tor: the reference sizes its "
+                                      "observation to 26 and writes 10, so it does not run there either; use osc")
         if self.control_type != "osc":
             raise ValueError("Invalid control type specified. Must be one of: {osc, joint_tor}")
         if self.cfg["task"]["randomize"]:
-            raise NotImplementedError("Houndarm domain randomisation (task.randomize) is outside the hot-path scope")
+            raise NotImplementedError(f"{type(self).__name__} domain randomisation (task.randomize) is outside the "
+                                      "hot-path scope")
         env["numObservations"] = ARM_OBS
         env["numActions"] = ARM_ACTIONS
         self.up_axis, self.up_axis_idx = "z", 2
@@ -78,10 +85,11 @@ class Houndarm(VecTask):
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
         dev, n = self.device, self.num_envs
-        self.default_dof_pos = to_torch([0, 0, 0, 0, 0, 0], device=dev)
+        nd = self.arm_dofs
+        self.default_dof_pos = to_torch(self.default_pose, device=dev)
         self.kp = to_torch([150.0] * 6, device=dev)
         self.kd = 2 * torch.sqrt(self.kp)
-        self.kp_null = to_torch([10.0] * 6, device=dev)
+        self.kp_null = to_torch([10.0] * nd, device=dev)
         self.kd_null = 2 * torch.sqrt(self.kp_null)
         self.cmd_limit = to_torch([0.1, 0.1, 0.1, 0.5, 0.5, 0.5], device=dev).unsqueeze(0)
         self.commands = torch.zeros(n, 3, dtype=torch.float, device=dev, requires_grad=False)
@@ -92,8 +100,8 @@ class Houndarm(VecTask):
         self._kernels = None
         if self.device != "cpu":
             # GPU pipeline: the controller, observations + reward + time-out mask, and reset_idx are one kernel each
-            from ...gymtask import ArmKernels  # fails loudly when libgymtask.so is missing
-            self._kernels = ArmKernels(self)
+            from ... import gymtask  # fails loudly when libgymtask.so is missing
+            self._kernels = getattr(gymtask, self.kernels_class)(self)
 
     # ------------------------------------------------------------------ scene
     def create_sim(self):
@@ -108,7 +116,7 @@ class Houndarm(VecTask):
     def _asset_options(self):
         opts = gymapi.AssetOptions()
         opts.replace_cylinder_with_capsule = False
-        opts.flip_visual_attachments = False
+        opts.flip_visual_attachments = self.flip_visual_attachments
         opts.fix_base_link = True
         opts.collapse_fixed_joints = False
         opts.disable_gravity = True  # (the OSC has no gravity compensation)
@@ -122,12 +130,12 @@ class Houndarm(VecTask):
         here = os.path.dirname(os.path.abspath(__file__))
         asset = self.cfg["env"].get("asset", {})
         root = os.path.join(here, asset.get("assetRoot", ASSET_ROOT))
-        file = asset.get("assetFileNamehoundarm", ASSET_FILE)
+        file = asset.get(self.asset_file_key, self.asset_file)
         if not os.path.isfile(os.path.join(root, file)):
             raise FileNotFoundError(
-                f"Houndarm asset not found: {os.path.join(root, file)}.  The arm's model is not shipped with the "
-                f"package: point env.asset.assetRoot and env.asset.assetFileNamehoundarm at the reference's "
-                f"{ASSET_FILE} or at a packed *.model.json of it (tools/pack_assets.py)")
+                f"{type(self).__name__} asset not found: {os.path.join(root, file)}.  The arm's model is not shipped "
+                f"with the package: point env.asset.assetRoot and env.asset.{self.asset_file_key} at the reference's "
+                f"{self.asset_file} or at a packed *.model.json of it (tools/pack_assets.py)")
         return root, file
 
     def _create_envs(self, num_envs, spacing, num_per_row):
@@ -176,9 +184,10 @@ class Houndarm(VecTask):
         self.eef_state = self.rigid_body_state[:, self.eef_index, :]
         # fixed base: [n, links - 1, 6, 6], the welded root's row dropped; the joint6 row is the end link's
         self.jacobian_full = gymtorch.wrap_tensor(self.gym.acquire_jacobian_tensor(self.sim, self.actor_name))
-        self.j_eef = self.jacobian_full[:, self.hand_joint_index, :, :6]
+        nd = self.arm_dofs
+        self.j_eef = self.jacobian_full[:, self.hand_joint_index, :, :nd]
         self.mass_matrix = gymtorch.wrap_tensor(self.gym.acquire_mass_matrix_tensor(self.sim, self.actor_name))
-        self.mm = self.mass_matrix[:, :6, :6]
+        self.mm = self.mass_matrix[:, :nd, :nd]
         self.pos_control = torch.zeros((n, self.num_dofs), dtype=torch.float, device=self.device)
         self.effort_control = torch.zeros_like(self.pos_control)
         self.global_indices = torch.arange(n, dtype=torch.int32, device=self.device).view(n, -1)
@@ -186,17 +195,18 @@ class Houndarm(VecTask):
     # ------------------------------------------------------------------ step
     def compute_osc_torques(self, dpose):
         """hound_arm.py:462-493 (Khatib's operational-space formulation with a null-space posture term)."""
-        q, qd = self.dof_pos[:, :6], self.dof_vel[:, :6]
+        nd = self.arm_dofs
+        q, qd = self.dof_pos[:, :nd], self.dof_vel[:, :nd]
         j_eef_t = torch.transpose(self.j_eef, 1, 2)
         mm_inv = torch.inverse(self.mm)
         m_eef_inv = self.j_eef @ mm_inv @ j_eef_t
         m_eef = torch.inverse(m_eef_inv)
         u = j_eef_t @ m_eef @ (self.kp * dpose - self.kd * self.eef_state[:, 7:]).unsqueeze(-1)
         j_eef_inv = m_eef @ self.j_eef @ mm_inv
-        u_null = self.kd_null * -qd + self.kp_null * ((self.default_dof_pos[:6] - q + np.pi) % (2 * np.pi) - np.pi)
+        u_null = self.kd_null * -qd + self.kp_null * ((self.default_dof_pos[:nd] - q + np.pi) % (2 * np.pi) - np.pi)
         u_null = self.mm @ u_null.unsqueeze(-1)
-        u += (torch.eye(6, device=self.device).unsqueeze(0) - j_eef_t @ j_eef_inv) @ u_null
-        return tensor_clamp(u.squeeze(-1), -self.effort_limits[:6].unsqueeze(0), self.effort_limits[:6].unsqueeze(0))
+        u += (torch.eye(nd, device=self.device).unsqueeze(0) - j_eef_t @ j_eef_inv) @ u_null
+        return tensor_clamp(u.squeeze(-1), -self.effort_limits[:nd].unsqueeze(0), self.effort_limits[:nd].unsqueeze(0))
 
     def pre_physics_step(self, actions):
         self.actions = actions.clone().to(self.device)
@@ -205,7 +215,7 @@ class Houndarm(VecTask):
             self._kernels.control(self.actions, self.sim.dof_force)
             return
         dpose = self.actions * self.cmd_limit / self.action_scale
-        self.effort_control[:, :6] = self.compute_osc_torques(dpose)
+        self.effort_control[:, :self.arm_dofs] = self.compute_osc_torques(dpose)
         self.gym.set_dof_actuation_force_tensor(self.sim, gymtorch.unwrap_tensor(self.effort_control))
 
     def post_physics_step(self):
@@ -245,15 +255,20 @@ class Houndarm(VecTask):
             self.reset_buf, self.progress_buf, self.eef_state, self.commands, self.reward_settings["r_dist_scale"],
             self.reward_settings["r_vel_scale"], self.max_episode_length)
 
+    def _after_reset_clamp(self, pos):
+        """What a subclass does to the clamped reset positions before they are written (Houndarm: nothing)."""
+        return pos
+
     def reset_idx(self, env_ids):
         k = len(env_ids)
         # (.squeeze() of a (1, 1) draw is 0-d: a reset of exactly one env broadcasts it)
         for column, (lo, hi) in ((self.commands_x, self.command_x_range), (self.commands_y, self.command_y_range),
                                  (self.commands_z, self.command_z_range)):
             column[env_ids] = torch_rand_float(lo, hi, (k, 1), device=self.device).squeeze()
-        noise = torch.rand((k, 6), device=self.device)
+        noise = torch.rand((k, self.arm_dofs), device=self.device)
         pos = tensor_clamp(self.default_dof_pos.unsqueeze(0) + self.dof_noise * 2.0 * (noise - 0.5),
                            self.dof_lower_limits.unsqueeze(0), self.dof_upper_limits)
+        pos = self._after_reset_clamp(pos)
         self.dof_pos[env_ids, :] = pos
         self.dof_vel[env_ids, :] = torch.zeros_like(self.dof_vel[env_ids])
         self.pos_control[env_ids, :] = pos

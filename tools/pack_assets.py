@@ -28,10 +28,12 @@ SOURCES = {
     "hound_new.model.json": "urdf/Hound_new/Hound.urdf",
 }
 # models that are test fixtures only (tests/golden/), not shipped with the package: the Houndarm task's fixed-base
-# Open Manipulator P (hound_arm.py:201), which a user loads from the reference's own URDF
+# Open Manipulator P (hound_arm.py:201) and the Manipulator task's Franka Panda (manipulator.py:199; .obj collision
+# meshes and no inertials: the masses come from the hulls at load time), which a user loads from the reference's own URDF
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 GOLDEN_SOURCES = {
     "open_manipulator_p.model.json": "urdf/open_manipulator_p_gazebo/urdf/open_manipulator_p.urdf",
+    "franka_panda_manipulator.model.json": "urdf/franka_description/robots/franka_panda_manipulator.urdf",
 }
 
 
