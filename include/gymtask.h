@@ -333,6 +333,63 @@ typedef struct gt_ant_reset_args {
 int gt_ant_reset_flagged(const gt_ant_params *p, const gt_ant_buffers *b, int k, const gt_ant_reset_args *r,
                          void *stream);
 
+/* ---- Humanoid (tasks/humanoid.py), fused; additive entry points, no ABI bump.
+ *
+ * gt_humanoid_post_physics: compute_humanoid_observations + compute_humanoid_reward (humanoid.py:324-413) in one
+ * launch, one env per lane, after post_physics_step's resets and its four refreshes.  Per env it writes the
+ * observation (width 24 + 4 * num_dofs, 108 at the body's 21 dofs: height, local velocity, local angular velocity *
+ * angular_velocity_scale, yaw, roll, angle to target -- the three normalised to (-pi, pi] --, up and heading
+ * projections, scaled dof positions, dof velocities * dof_vel_scale, DOF forces * contact_force_scale, the 12 sensor
+ * values * contact_force_scale, actions), potentials / previous potentials, up and heading vectors, the reward (the
+ * joint-limit and electricity costs weighted per dof by motor_efforts / max_motor_effort) and the done mask (int64:
+ * fallen or episode end, else kept); the done count goes to host_count as gt_ant_post_physics publishes it.
+ * root_states [N][13], dof_state [N*nd][2], dof_force [N][nd], sensors [N][12], actions [N][nd], targets [N][3],
+ * inv_start_rot [N][4], potentials / prev_potentials / rew_buf [N], up_vec / heading_vec [N][3],
+ * obs_buf [N][24 + 4 nd], reset_buf / progress_buf int64 [N].  Per-dof arrays hold GT_HUMANOID_MAXD entries;
+ * 1 <= num_dofs <= GT_HUMANOID_MAXD is checked. */
+#define GT_HUMANOID_MAXD 32
+#define GT_HUMANOID_SENSOR_VALUES 12
+
+typedef struct gt_humanoid_params {
+    int32_t num_envs, num_dofs;
+    float dt, dof_vel_scale, contact_force_scale, angular_velocity_scale, heading_weight, up_weight,
+          actions_cost_scale, energy_cost_scale, joints_at_limit_cost_scale, termination_height, death_cost,
+          max_episode_length, max_motor_effort;
+    float dof_lower[GT_HUMANOID_MAXD], dof_upper[GT_HUMANOID_MAXD], motor_efforts[GT_HUMANOID_MAXD];
+} gt_humanoid_params;
+
+typedef struct gt_humanoid_buffers {
+    const float *root_states, *dof_state, *dof_force, *sensors, *actions, *targets, *inv_start_rot;
+    float *potentials, *prev_potentials, *up_vec, *heading_vec, *obs_buf, *rew_buf;
+    int64_t *reset_buf;
+    const int64_t *progress_buf;
+    int32_t *reset_count;        /* [3] device, zero-initialised accumulator (re-armed by the kernel) */
+    int32_t *host_count;         /* [2] host-mapped {count, seq} or NULL */
+    int32_t seq;
+    uint64_t *reset_masks;       /* [ceil(N/64)] the done mask's per-wave ballots (gt_humanoid_reset_flagged) */
+} gt_humanoid_buffers;
+
+int gt_humanoid_post_physics(const gt_humanoid_params *p, const gt_humanoid_buffers *b, void *stream);
+
+/* Humanoid reset_idx (humanoid.py:253-279), fused, for the k envs the previous gt_humanoid_post_physics flagged (its
+ * reset_masks ballots; env ids ascending = torch's nonzero order): gt_ant_reset_flagged's steps at num_dofs dofs --
+ * the two torch_rand_float draws [k][nd] from two consecutive torch.rand plans evaluated in-kernel (or explicit
+ * uniforms u_pos / u_vel), the clamp into the limits, potentials, counters, env_ids_out[rank] = e.  The caller then
+ * applies the reference's two indexed state sets. */
+typedef struct gt_humanoid_reset_args {
+    gt_torch_rand_plan plan_pos, plan_vel;
+    const float *u_pos, *u_vel;
+    float pos_range, pos_lower, vel_range, vel_lower;
+    const float *initial_dof_pos;      /* [N][nd] */
+    const float *initial_root_states;  /* [N][13] */
+    float *dof_state;                  /* [N*nd][2] the task's dof tensor */
+    int64_t *progress_buf;             /* [N] */
+    int32_t *env_ids_out;              /* [>= k] */
+} gt_humanoid_reset_args;
+
+int gt_humanoid_reset_flagged(const gt_humanoid_params *p, const gt_humanoid_buffers *b, int k,
+                              const gt_humanoid_reset_args *r, void *stream);
+
 /* ---- the flat-ground tasks Anymal and Hound (tasks/anymal.py), fused; additive entry points, no ABI bump.
  *
  * gt_flat_post_physics: compute_observations + compute_reward (anymal.py:241-276, 312-386) in one launch, one env per

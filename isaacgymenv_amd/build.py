@@ -20,7 +20,8 @@ ARCH = os.environ.get("GS_OFFLOAD_ARCH", "gfx950")
 LIBS = {
     "libgymsim.so": ["gs_physics.hip", "gs_phys_inst.hip", "gs_team.hip", "gs_kinematics.hip", "gs_host.hip",
                      "gs_generic.hip", "gs_model_pack.hip", "gs_terrain_build.hip", "gs_capi.hip"],
-    "libgymtask.so": ["gt_anymal.hip", "gt_hound.hip", "gt_ant.hip", "gt_anymal_flat.hip", "gt_arm.hip", "gt_manip.hip"],
+    "libgymtask.so": ["gt_anymal.hip", "gt_hound.hip", "gt_ant.hip", "gt_anymal_flat.hip", "gt_arm.hip", "gt_manip.hip",
+                      "gt_humanoid.hip"],
     "libgymrl.so": ["rl_gae.hip", "rl_grad.hip", "rl_rollout.hip", "rl_ppo_loss.hip", "rl_rms.hip", "rl_adam.hip", "rl_linear.hip",
                    "rl_policy.hip", "rl_infer.hip"],
 }
@@ -35,7 +36,7 @@ EXTRA_FLAGS = {"libgymtask.so": ["-ffp-contract=off"], "libgymrl.so": ["-ffp-con
                "libgymsim_prof.so": SIM_FLAGS + ["-DGS_PHASE_PROFILE"]}
 HEADERS = ["gs_internal.h", "gs_topologies.h", "gs_math.h", "gs_terrain.h", "gs_pairs.h", "gs_solver.h", "gs_kinematics.h", "gs_host_impl.h",
            "gs_physics_impl.h", "torch_philox.h", "gt_anymal_tail.h", "gt_wave.h", "gt_host.h", "gs_kernel_choice.h",
-           "gs_model_pack.h", "gs_terrain_build.h", "gt_osc6.h"]
+           "gs_model_pack.h", "gs_terrain_build.h", "gt_osc6.h", "gt_loco.h"]
 # gs_phys_inst.hip is compiled once per (topology, kernel form): 0 simulate plane, 1 simulate terrain-mesh,
 # 2 fused PD step plane, 3 fused PD step terrain-mesh (gs_physics_impl.h); 4-7 the same four with the DOF force
 # store compiled in (launched only while a sim has the tensor bound)

@@ -135,6 +135,30 @@ class GtAntResetArgs(C.Structure):
                                   "env_ids_out")]
 
 
+GT_HUMANOID_MAXD = 32  # gymtask.h: entries of the per-dof arrays in gt_humanoid_params
+
+
+class GtHumanoidParams(C.Structure):
+    _fields_ = [("num_envs", C.c_int32), ("num_dofs", C.c_int32)] + [
+        (n, C.c_float) for n in ("dt", "dof_vel_scale", "contact_force_scale", "angular_velocity_scale",
+                                 "heading_weight", "up_weight", "actions_cost_scale", "energy_cost_scale",
+                                 "joints_at_limit_cost_scale", "termination_height", "death_cost",
+                                 "max_episode_length", "max_motor_effort")] + [
+        (n, C.c_float * GT_HUMANOID_MAXD) for n in ("dof_lower", "dof_upper", "motor_efforts")]
+
+
+class GtHumanoidBuffers(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("root_states", "dof_state", "dof_force", "sensors", "actions", "targets",
+                                          "inv_start_rot", "potentials", "prev_potentials", "up_vec",
+                                          "heading_vec", "obs_buf", "rew_buf", "reset_buf", "progress_buf",
+                                          "reset_count", "host_count")] + [("seq", C.c_int32),
+                                                                           ("reset_masks", C.c_void_p)]
+
+
+class GtHumanoidResetArgs(C.Structure):
+    _fields_ = list(GtAntResetArgs._fields_)  # the same members; the draws are [k][num_dofs]
+
+
 class GtFlatParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_envs", "num_dofs", "num_bodies", "base_index", "num_knees")] + [
         ("knee_idx", C.c_int32 * 8), ("max_episode_length", C.c_int32)] + [
@@ -300,6 +324,9 @@ def _argtypes():
             "gt_ant_post_physics": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), vp],
             "gt_ant_reset_flagged": [C.POINTER(GtAntParams), C.POINTER(GtAntBuffers), i,
                                      C.POINTER(GtAntResetArgs), vp],
+            "gt_humanoid_post_physics": [C.POINTER(GtHumanoidParams), C.POINTER(GtHumanoidBuffers), vp],
+            "gt_humanoid_reset_flagged": [C.POINTER(GtHumanoidParams), C.POINTER(GtHumanoidBuffers), i,
+                                          C.POINTER(GtHumanoidResetArgs), vp],
             "gt_flat_post_physics": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), vp],
             "gt_flat_reset_flagged": [C.POINTER(GtFlatParams), C.POINTER(GtFlatBuffers), i,
                                       C.POINTER(GtFlatResetArgs), vp],
@@ -411,6 +438,34 @@ class _FusedTail:
         _check(self._post(C.byref(self.p), C.byref(b), C.c_void_p(stream)), self.POST)
         self._launched = True
 
+    def _reset_flagged_dof_draws(self, entry, args_class, k: int, u_pos=None, u_vel=None):
+        """reset_idx of Ant and Humanoid (ant.py:252-279, humanoid.py:253-279) for the k envs the previous launch
+        flagged, in one kernel (`entry`, taking an `args_class` struct): the two torch_rand_float draws [k, num_dof]
+        evaluated in-kernel from the device generator (advanced exactly as torch.rand would be) or taken from u_pos /
+        u_vel, the clamped dof state, potentials, counters; then the reference's two indexed state sets.  Returns the
+        flagged env ids (int32 [k])."""
+        from .isaacgym import gymtorch
+        t = self.env
+        r = args_class()
+        if u_pos is None:
+            r.plan_pos, r.plan_vel = self.planner.plan_many((k * t.num_dof, k * t.num_dof))
+        else:
+            u_pos, u_vel = u_pos.contiguous(), u_vel.contiguous()
+            r.u_pos, r.u_vel = u_pos.data_ptr(), u_vel.data_ptr()
+        # torch_rand_float(lower, upper): (upper - lower) * rand + lower, the range a Python double
+        r.pos_range, r.pos_lower = 0.2 - (-0.2), -0.2
+        r.vel_range, r.vel_lower = 0.1 - (-0.1), -0.1
+        r.initial_dof_pos, r.initial_root_states = t.initial_dof_pos.data_ptr(), t.initial_root_states.data_ptr()
+        r.dof_state, r.progress_buf, r.env_ids_out = t.dof_state.data_ptr(), t.progress_buf.data_ptr(), \
+            self.env_ids.data_ptr()
+        stream = raw_stream(t.root_states.device)
+        _check(getattr(lib(), entry)(C.byref(self.p), C.byref(self._buffers()), k, C.byref(r), C.c_void_p(stream)), entry)
+        ids = self.env_ids[:k]
+        t.gym.set_actor_root_state_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.initial_root_states),
+                                                  gymtorch.unwrap_tensor(ids), k)
+        t.gym.set_dof_state_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.dof_state), gymtorch.unwrap_tensor(ids), k)
+        return ids
+
 
 class AntTailKernel(_FusedTail):
     """gt_ant_post_physics bound to one Ant env (GPU pipeline): observations + reward + done mask in one
@@ -434,31 +489,8 @@ class AntTailKernel(_FusedTail):
         self.true_objective = torch.zeros(t.num_envs, dtype=torch.float32, device=t.device)
 
     def reset_flagged(self, k: int, u_pos=None, u_vel=None):
-        """ant.py:252-279 reset_idx for the k envs the previous launch flagged, in one kernel: the two
-        torch_rand_float draws evaluated in-kernel from the device generator (advanced exactly as torch.rand
-        would be) or taken from u_pos / u_vel [k, 8], the clamped dof state, potentials, counters; then the
-        reference's two indexed state sets.  Returns the flagged env ids (int32 [k])."""
-        from .isaacgym import gymtorch
-        t = self.env
-        r = GtAntResetArgs()
-        if u_pos is None:
-            r.plan_pos, r.plan_vel = self.planner.plan_many((k * t.num_dof, k * t.num_dof))
-        else:
-            r.u_pos, r.u_vel = u_pos.contiguous().data_ptr(), u_vel.contiguous().data_ptr()
-        # torch_rand_float(lower, upper): (upper - lower) * rand + lower, the range a Python double
-        r.pos_range, r.pos_lower = 0.2 - (-0.2), -0.2
-        r.vel_range, r.vel_lower = 0.1 - (-0.1), -0.1
-        r.initial_dof_pos, r.initial_root_states = t.initial_dof_pos.data_ptr(), t.initial_root_states.data_ptr()
-        r.dof_state, r.progress_buf, r.env_ids_out = t.dof_state.data_ptr(), t.progress_buf.data_ptr(), \
-            self.env_ids.data_ptr()
-        stream = raw_stream(t.root_states.device)
-        _check(lib().gt_ant_reset_flagged(C.byref(self.p), C.byref(self._buffers()), k, C.byref(r),
-                                          C.c_void_p(stream)), "gt_ant_reset_flagged")
-        ids = self.env_ids[:k]
-        t.gym.set_actor_root_state_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.initial_root_states),
-                                                  gymtorch.unwrap_tensor(ids), k)
-        t.gym.set_dof_state_tensor_indexed(t.sim, gymtorch.unwrap_tensor(t.dof_state), gymtorch.unwrap_tensor(ids), k)
-        return ids
+        """gt_ant_reset_flagged (_FusedTail._reset_flagged_dof_draws)."""
+        return self._reset_flagged_dof_draws("gt_ant_reset_flagged", GtAntResetArgs, k, u_pos, u_vel)
 
     def tensors(self):
         t = self.env
@@ -467,6 +499,48 @@ class AntTailKernel(_FusedTail):
                 ("potentials", t.potentials), ("prev_potentials", t.prev_potentials), ("up_vec", t.up_vec),
                 ("heading_vec", t.heading_vec), ("obs_buf", t.obs_buf), ("rew_buf", t.rew_buf),
                 ("true_objective", self.true_objective), ("reset_buf", t.reset_buf), ("progress_buf", t.progress_buf))
+
+
+class HumanoidTailKernel(_FusedTail):
+    """gt_humanoid_post_physics / gt_humanoid_reset_flagged bound to one Humanoid env (GPU pipeline): the 108-wide
+    observation, reward and done mask in one launch with the done count published to pinned host memory, and
+    reset_idx of the flagged envs in one launch plus the reference's two indexed state sets."""
+
+    POST, BUFFERS = "gt_humanoid_post_physics", GtHumanoidBuffers
+
+    def __init__(self, env):
+        t = env
+        nd = int(t.num_dof)
+        if not 1 <= nd <= GT_HUMANOID_MAXD:
+            raise ValueError(f"gt_humanoid_params holds at most {GT_HUMANOID_MAXD} dofs, the asset has {nd}")
+        assert t.obs_buf.shape[1] == 24 + 4 * nd and t.vec_sensor_tensor.shape[1] == 12
+        p = GtHumanoidParams()
+        p.num_envs, p.num_dofs = t.num_envs, nd
+        p.dt, p.dof_vel_scale, p.contact_force_scale = float(t.dt), float(t.dof_vel_scale), float(t.contact_force_scale)
+        p.angular_velocity_scale = float(t.angular_velocity_scale)
+        p.heading_weight, p.up_weight = float(t.heading_weight), float(t.up_weight)
+        p.actions_cost_scale, p.energy_cost_scale = float(t.actions_cost_scale), float(t.energy_cost_scale)
+        p.joints_at_limit_cost_scale = float(t.joints_at_limit_cost_scale)
+        p.termination_height, p.death_cost = float(t.termination_height), float(t.death_cost)
+        p.max_episode_length = float(t.max_episode_length)
+        p.max_motor_effort = float(t.max_motor_effort)
+        for dst, src in ((p.dof_lower, t.dof_limits_lower), (p.dof_upper, t.dof_limits_upper),
+                         (p.motor_efforts, t.motor_efforts)):
+            dst[:nd] = [float(v) for v in src.cpu()]
+        super().__init__(env, p)
+
+    def reset_flagged(self, k: int, u_pos=None, u_vel=None):
+        """gt_humanoid_reset_flagged (_FusedTail._reset_flagged_dof_draws)."""
+        return self._reset_flagged_dof_draws("gt_humanoid_reset_flagged", GtHumanoidResetArgs, k, u_pos, u_vel)
+
+    def tensors(self):
+        t = self.env
+        return (("root_states", t.root_states), ("dof_state", t.dof_state), ("dof_force", t.dof_force_tensor),
+                ("sensors", t.vec_sensor_tensor), ("actions", t.actions), ("targets", t.targets),
+                ("inv_start_rot", t.inv_start_rot), ("potentials", t.potentials),
+                ("prev_potentials", t.prev_potentials), ("up_vec", t.up_vec), ("heading_vec", t.heading_vec),
+                ("obs_buf", t.obs_buf), ("rew_buf", t.rew_buf), ("reset_buf", t.reset_buf),
+                ("progress_buf", t.progress_buf))
 
 
 class FlatTailKernel(_FusedTail):

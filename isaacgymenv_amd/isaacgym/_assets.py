@@ -266,6 +266,9 @@ class RawLink:
     # collision <mesh> files the importer could not read as STL or .obj (gym.load_asset warns
     # with the link names)
     dropped_meshes: List[str] = field(default_factory=list)
+    # a link the importer put between the joints of a multi-joint MJCF body (_mjcf.py): no mass, no shapes, and not
+    # one of the rigid bodies the API reports
+    hidden: bool = False
 
 
 @dataclass
@@ -285,6 +288,7 @@ class RawJoint:
     friction: float = 0.0
     armature: Optional[float] = None   # MJCF joint armature (URDF: AssetOptions.armature)
     motor_gear: float = 0.0            # MJCF <motor gear>: the DOF's motor_effort
+    stiffness: float = 0.0             # MJCF joint stiffness: the DOF properties' field (acts in DOF_MODE_POS only)
 
 
 @dataclass
@@ -294,6 +298,8 @@ class RawModel:
     link_order: List[str]
     joints: List[RawJoint]
     default_friction: float = 1.0      # rigid shape friction the importer assigns (MJCF geom friction[0])
+    document_order: bool = False       # siblings keep link_order (MJCF) instead of being sorted by name
+    actuator_order: Optional[List[str]] = None  # motorised joints in <actuator> order (None: DOF order)
 
     # ---- (de)serialisation of the packed form shipped under assets/ ----
     def to_json(self) -> dict:
@@ -308,15 +314,23 @@ class RawModel:
                 inert = {"mass": l.inertial.mass, "com": l.inertial.com.tolist(),
                          "inertia": l.inertial.inertia.tolist()}
             links.append({"name": n, "inertial": inert, "shapes": [shp(s) for s in l.shapes],
-                          "dropped_meshes": list(l.dropped_meshes)})
+                          "dropped_meshes": list(l.dropped_meshes), **({"hidden": True} if l.hidden else {})})
+        # (hidden, stiffness, document_order, actuator_order: written only where set, so a model without them
+        # keeps the text it was packed with)
         joints = [{"name": j.name, "kind": j.kind, "parent": j.parent, "child": j.child,
                    "origin": j.origin.to_json(), "axis": j.axis.tolist(), "lower": j.lower,
                    "upper": j.upper, "has_limits": j.has_limits, "effort": j.effort,
                    "velocity": j.velocity, "damping": j.damping, "friction": j.friction,
-                   "armature": j.armature, "motor_gear": j.motor_gear}
+                   "armature": j.armature, "motor_gear": j.motor_gear,
+                   **({"stiffness": j.stiffness} if j.stiffness else {})}
                   for j in self.joints]
+        extra = {}
+        if self.document_order:
+            extra["document_order"] = True
+        if self.actuator_order is not None:
+            extra["actuator_order"] = list(self.actuator_order)
         return {"format": "isaacgymenv_amd.raw_model/1", "name": self.name, "links": links, "joints": joints,
-                "default_friction": self.default_friction}
+                "default_friction": self.default_friction, **extra}
 
     @staticmethod
     def from_json(d: dict) -> "RawModel":
@@ -327,13 +341,15 @@ class RawModel:
                 inert = RawInertial(l["inertial"]["mass"], np.array(l["inertial"]["com"]),
                                     np.array(l["inertial"]["inertia"]))
             shapes = [RawShape(s["kind"], Pose.from_json(s["pose"]), list(s["size"])) for s in l["shapes"]]
-            links[l["name"]] = RawLink(l["name"], inert, shapes, list(l.get("dropped_meshes", [])))
+            links[l["name"]] = RawLink(l["name"], inert, shapes, list(l.get("dropped_meshes", [])),
+                                       bool(l.get("hidden", False)))
             order.append(l["name"])
         joints = [RawJoint(j["name"], j["kind"], j["parent"], j["child"], Pose.from_json(j["origin"]),
                            np.array(j["axis"], dtype=np.float64), j["lower"], j["upper"], j["has_limits"],
                            j["effort"], j["velocity"], j["damping"], j["friction"], j.get("armature"),
-                           j.get("motor_gear", 0.0)) for j in d["joints"]]
-        return RawModel(d["name"], links, order, joints, d.get("default_friction", 1.0))
+                           j.get("motor_gear", 0.0), j.get("stiffness", 0.0)) for j in d["joints"]]
+        return RawModel(d["name"], links, order, joints, d.get("default_friction", 1.0),
+                        bool(d.get("document_order", False)), d.get("actuator_order"))
 
 
 _FLOAT_PREFIX = re.compile(r"^\s*[-+]?(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?")
@@ -485,6 +501,7 @@ class Dof:
     friction: float
     armature: Optional[float] = None  # per-dof (MJCF); None: AssetOptions.armature
     motor_gear: float = 0.0           # MJCF motor gear (actuator motor_effort)
+    stiffness: float = 0.0            # MJCF joint stiffness (the DOF properties' field)
 
 
 @dataclass
@@ -498,6 +515,7 @@ class Link:
     pose: "Pose"              # link frame in the body frame
     mass: float
     com: np.ndarray           # link COM in the link frame
+    hidden: bool = False      # between the joints of a multi-joint MJCF body: simulated, never reported
 
 
 @dataclass
@@ -512,6 +530,8 @@ class Articulation:
     links: Optional[List[Link]] = None
     # link of every shape, in shape order (None: the shape's body)
     shape_links: Optional[List[int]] = None
+    # motorised DOFs in the asset's <actuator> order (MJCF), None: DOF order
+    actuator_dofs: Optional[List[int]] = None
 
     @property
     def num_bodies(self):
@@ -529,8 +549,19 @@ class Articulation:
     def num_links(self):
         return len(self.links) if self.links is not None else len(self.bodies)
 
+    @property
+    def num_hidden_links(self):
+        return sum(1 for l in self.links if l.hidden) if self.links is not None else 0
+
+    @property
+    def num_public_links(self):
+        """Rigid bodies the API reports: the link table without its hidden links (they sit after the named ones, so
+        a reported index is the link table's)."""
+        return self.num_links - self.num_hidden_links
+
     def link_names(self):
-        return [l.name for l in self.links] if self.links is not None else self.body_names()
+        """Names of the reported rigid bodies (hidden links have none to report)."""
+        return [l.name for l in self.links if not l.hidden] if self.links is not None else self.body_names()
 
     def link_table(self) -> List[Link]:
         """Every reported rigid body with its dynamic body and pose (identity when links = bodies)."""
@@ -618,6 +649,11 @@ class Articulation:
         tab = self.shape_table()
         lt = self.link_table()
         lpar = [l.parent for l in lt]
+        # two links joined through hidden links only are jointed neighbours too (PhysX sees one spherical joint
+        # where a multi-joint MJCF body hangs): a link's parent is its nearest reported ancestor
+        for i in range(len(lpar)):
+            while lpar[i] >= 0 and lt[lpar[i]].hidden:
+                lpar[i] = lt[lpar[i]].parent
         out = []
         for a in range(len(tab)):
             for b in range(a + 1, len(tab)):
@@ -728,8 +764,19 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
     # collapse_fixed_joints=False with fixed joints present: the dynamics weld every fixed link into
     # its parent (a rigid weld has no dynamics of its own) while the tensor API keeps reporting each
     # link (Isaac Gym's rigid-body count, names, contact forces and Jacobian rows are per link)
-    keep_links = not collapse and any(j.kind == JOINT_FIXED for j in raw.joints)
+    has_hidden = any(l.hidden for l in raw.links.values())
+    keep_links = (not collapse and any(j.kind == JOINT_FIXED for j in raw.joints)) or has_hidden
     weld = collapse or keep_links
+    # siblings by name (URDF), or in the order of the file (an MJCF whose document order differs)
+    rank = {n: i for i, n in enumerate(raw.link_order)}
+    sib = (lambda jj: rank[jj.child]) if raw.document_order else (lambda jj: jj.child)
+    for j in raw.joints:
+        # the hidden link a joint carries has no inertia of its own: only the joint's armature keeps the mass
+        # matrix positive definite there
+        arm = float(opt["armature"]) if j.armature is None else float(j.armature)
+        if raw.links[j.child].hidden and arm <= 0.0:
+            raise ValueError(f"asset {raw.name}: joint {j.name} of a multi-joint body has zero armature; the massless "
+                             f"link it carries would make the mass matrix singular")
     member_of: Dict[str, tuple] = {}
     derived: Dict[str, RawInertial] = {}
     shape_link_names: List[str] = []
@@ -743,7 +790,7 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
         movable_children = []
         while stack:
             ln, pose = stack.pop(0)
-            for j in sorted(children.get(ln, []), key=lambda jj: jj.child):
+            for j in sorted(children.get(ln, []), key=sib):
                 if j.kind == JOINT_FIXED and weld:
                     p = pose.compose(j.origin)
                     members.append((j.child, p))
@@ -779,7 +826,7 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
             b = Body(link_name, parent_idx, joint.kind, joint.name, joint.origin, joint.axis.copy(), m, c, I, shapes)
         bodies.append(b)
         # children visited depth-first, siblings sorted by body name
-        for pose, j in sorted(movable_children, key=lambda pj: pj[1].child):
+        for pose, j in sorted(movable_children, key=lambda pj: sib(pj[1])):
             jj = RawJoint(**{**j.__dict__, "origin": pose.compose(j.origin)})
             make_body(j.child, idx, jj)
         return idx
@@ -790,11 +837,14 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
         if b.joint_kind in (JOINT_REVOLUTE, JOINT_PRISMATIC):
             j = next(jj for jj in raw.joints if jj.name == b.joint_name)
             dofs.append(Dof(j.name, bi, j.kind, j.lower, j.upper, j.has_limits, j.effort, j.velocity,
-                            j.damping, j.friction, j.armature, j.motor_gear))
+                            j.damping, j.friction, j.armature, j.motor_gear, j.stiffness))
     # bodies with no mass (no inertial and no shapes, or a fixed base's welded root) get 1 g and a tiny inertia: keep
-    # M non-singular
+    # M non-singular.  Not the hidden links of a multi-joint body: they stay exactly massless (their joints' armature
+    # was checked above)
     for b in bodies:
-        if b.mass <= 0.0:
+        if raw.links[b.name].hidden:
+            b.mass, b.com, b.inertia = 0.0, np.zeros(3), np.zeros((3, 3))
+        elif b.mass <= 0.0:
             b.mass = 1e-3
             b.inertia = np.eye(3) * 1e-6
         else:
@@ -814,8 +864,8 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
             j = parent_joint.get(ln)
             links.append(Link(ln, parent_link, j.name if j is not None else "", bi, pose,
                               float(inert.mass) if inert is not None else 0.0,
-                              inert.com.copy() if inert is not None else np.zeros(3)))
-            for jj in sorted(children.get(ln, []), key=lambda x: x.child):
+                              inert.com.copy() if inert is not None else np.zeros(3), raw.links[ln].hidden))
+            for jj in sorted(children.get(ln, []), key=sib):
                 visit(jj.child, li)
 
         visit(roots[0], -1)
@@ -826,8 +876,22 @@ def build_articulation(raw: RawModel, options: Optional[dict] = None) -> Articul
         if link_dofs != [d.name for d in dofs]:
             raise ValueError(f"asset {raw.name}: welded DOF order {[d.name for d in dofs]} differs from the "
                              f"link order {link_dofs}")
+        if has_hidden:
+            # the reported links first, in their order, the hidden ones after them: a reported index stays what it is
+            # without the hidden links
+            perm = [i for i, l in enumerate(links) if not l.hidden] + [i for i, l in enumerate(links) if l.hidden]
+            new_of = {old: new for new, old in enumerate(perm)}
+            new_of[-1] = -1
+            links = [links[i] for i in perm]
+            for l in links:
+                l.parent = new_of[l.parent]
+            shape_links = [new_of[i] for i in shape_links]
+    actuator_dofs = None
+    if raw.actuator_order is not None:
+        names = [d.name for d in dofs]
+        actuator_dofs = [names.index(n) for n in raw.actuator_order]
     return Articulation(raw.name, bodies, dofs, bool(opt["fix_base_link"]), opt, raw.default_friction,
-                        links, shape_links)
+                        links, shape_links, actuator_dofs)
 
 
 # --------------------------------------------------------------------------

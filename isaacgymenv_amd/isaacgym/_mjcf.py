@@ -4,8 +4,10 @@ Replaces the MJCF importer inside the closed Isaac Gym binary that the reference
 through ``gym.load_asset(sim, root, "mjcf/nv_ant.xml", options)`` (``ant.py:149-157``).
 What the reference relies on, restated from MuJoCo's documented semantics:
 
-* ``<default>`` classes (the unnamed top-level default only): joint ``armature``,
-  ``damping``, ``limited``, ``range``; geom ``density``, ``friction``, ``size``.
+* ``<default>`` classes with nested inheritance: a body's ``childclass`` holds for its subtree, an
+  element's own ``class`` overrides it, the unnamed top-level default applies to everything; read for
+  ``joint`` (``armature``, ``damping``, ``stiffness``, ``limited``, ``range``, ...), ``geom`` (``type``,
+  ``density``, ``friction``, ``size``) and ``motor`` (``ctrlrange``, ``ctrllimited``).
 * ``<compiler angle="degree|radian" inertiafromgeom="true">``: joint ranges in degrees
   by default; body mass/inertia from the geoms' volumes times ``density``.
 * ``<body pos quat euler>`` frames (euler in degrees with the default ``eulerseq="xyz"``,
@@ -14,8 +16,13 @@ What the reference relies on, restated from MuJoCo's documented semantics:
   by ``pos``; the axis is expressed in the body frame).
 * ``<geom type="sphere|capsule|box|cylinder">`` with ``pos``/``quat`` or ``fromto``;
   capsule/cylinder ``size="r half_length"`` unless ``fromto`` is given.
+* several hinge / slide joints on one body (nv_humanoid.xml: the waist, hips, ankles and shoulders) act in
+  document order, each about its own ``pos``: joints 1..k-1 become hidden links without mass or shapes, the
+  body hangs on joint k; DOFs follow document order.  A body without a joint (the head, the hands) is a
+  fixed child of its parent.
 * ``<actuator><motor joint gear ctrlrange>``: the motor gear becomes the DOF's
-  ``motor_effort`` (``ant.py:160-162`` reads it through ``get_asset_actuator_properties``).
+  ``motor_effort`` (``ant.py:160-162`` reads it through ``get_asset_actuator_properties``), the
+  motors listed in ``<actuator>`` order (``humanoid.py:160-163``).
 * World-attached geoms (the floor plane) are not part of the actor.
 
 Bodies keep document (depth-first) order; for nv_ant.xml this coincides with the
@@ -30,7 +37,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._assets import (JOINT_FREE, JOINT_PRISMATIC, JOINT_REVOLUTE, SHAPE_BOX, SHAPE_CAPSULE, SHAPE_CYLINDER,
+from ._assets import (JOINT_FIXED, JOINT_FREE, JOINT_PRISMATIC, JOINT_REVOLUTE, SHAPE_BOX, SHAPE_CAPSULE, SHAPE_CYLINDER,
                       SHAPE_SPHERE, Pose, RawInertial, RawJoint, RawLink, RawModel, RawShape, quat_xyzw_to_mat)
 
 
@@ -107,40 +114,43 @@ def parse_mjcf(path: str) -> RawModel:
     comp = root.find("compiler")
     degrees = (comp.get("angle", "degree") if comp is not None else "degree") == "degree"
     from_geom = (comp.get("inertiafromgeom", "auto") if comp is not None else "auto") in ("true", "auto")
-    djoint: Dict[str, str] = {}
-    dgeom: Dict[str, str] = {}
-    dflt = root.find("default")
-    if dflt is not None:
-        if dflt.find("joint") is not None:
-            djoint = dict(dflt.find("joint").attrib)
-        if dflt.find("geom") is not None:
-            dgeom = dict(dflt.find("geom").attrib)
+    classes = _default_classes(root)
 
-    gears: Dict[str, float] = {}
+    def attrs(el, childclass: Optional[str]) -> Dict[str, str]:
+        """The element's attributes over its class's: its own ``class``, else the enclosing ``childclass``, else
+        the unnamed top-level default."""
+        cls = el.get("class") or childclass or MAIN_CLASS
+        if cls not in classes:
+            raise ValueError(f"{path}: unknown default class {cls!r}")
+        return {**classes[cls].get(el.tag, {}), **el.attrib}
+
+    gears: Dict[str, tuple] = {}
+    motors: List[str] = []  # motorised joints in <actuator> order
     act = root.find("actuator")
     if act is not None:
-        for mo in act.findall("motor"):
+        for me in act.findall("motor"):
+            mo = attrs(me, None)
             g = _vec(mo.get("gear"), 1, [1.0])[0] if mo.get("gear") is not None else 1.0
             cr = _vec(mo.get("ctrlrange"), 2, [-1.0, 1.0])
             gears[mo.get("joint")] = (g, max(abs(cr[0]), abs(cr[1])) if mo.get("ctrllimited", "false") == "true" else 0.0)
+            motors.append(mo.get("joint"))
 
     links: Dict[str, RawLink] = {}
     order: List[str] = []
     joints: List[RawJoint] = []
 
-    def geom_attr(g, k, default=None):
-        return g.get(k, dgeom.get(k, default))
-
-    def visit(be, parent_name: Optional[str], parent_frame_in_parent_link: Pose):
+    def visit(be, parent_name: Optional[str], parent_frame_in_parent_link: Pose, childclass: Optional[str]):
         name = be.get("name") or f"body{len(order)}"
+        childclass = be.get("childclass", childclass)
         frame = _frame(be, degrees)  # body frame in the parent body frame
         shapes: List[RawShape] = []
         m_tot, c_acc, I_tot = 0.0, np.zeros(3), np.zeros((3, 3))
         parts = []
-        for g in be.findall("geom"):
-            gtype = geom_attr(g, "type", "sphere")
-            rho = float(geom_attr(g, "density", 1000.0))
-            size = _vec(geom_attr(g, "size"), len(geom_attr(g, "size").split())) if geom_attr(g, "size") else [0.0]
+        for ge in be.findall("geom"):
+            g = attrs(ge, childclass)
+            gtype = g.get("type", "sphere")
+            rho = float(g.get("density", 1000.0))
+            size = _vec(g.get("size"), len(g.get("size").split())) if g.get("size") else [0.0]
             ft = g.get("fromto")
             if ft is not None and gtype in ("capsule", "cylinder"):
                 a, b = np.array(_vec(ft, 6)[:3]), np.array(_vec(ft, 6)[3:])
@@ -186,35 +196,52 @@ def parse_mjcf(path: str) -> RawModel:
         order.append(name)
 
         jels = [j for j in be if j.tag in ("joint", "freejoint")]
-        if parent_name is not None:
-            if len(jels) != 1:
-                raise ValueError(f"{path}: body {name} needs exactly one joint (has {len(jels)})")
-            je = jels[0]
-            jtype = je.get("type", djoint.get("type", "hinge")) if je.tag == "joint" else "free"
-            kind = {"hinge": JOINT_REVOLUTE, "slide": JOINT_PRISMATIC}.get(jtype)
-            if kind is None:
-                raise ValueError(f"{path}: joint type {jtype} on a non-root body is not supported")
-            axis = np.array(_vec(je.get("axis", djoint.get("axis")), 3, [0, 0, 1]), dtype=np.float64)
-            axis /= np.linalg.norm(axis)
-            jpos = np.array(_vec(je.get("pos", djoint.get("pos")), 3, [0, 0, 0]), dtype=np.float64)
-            limited = je.get("limited", djoint.get("limited", "false")) == "true"
-            rng = _vec(je.get("range", djoint.get("range")), 2, [0.0, 0.0])
-            if kind == JOINT_REVOLUTE and degrees:
-                rng = [math.radians(v) for v in rng]
-            jname = je.get("name") or f"joint{len(joints)}"
-            gear, ctrl = gears.get(jname, (0.0, 0.0))
-            # joint frame: body frame shifted by pos; the child link frame is re-expressed so that the
-            # joint sits at its origin (geoms/inertia are moved by -pos below)
-            origin = Pose(parent_frame_in_parent_link.R @ frame.R,
-                          parent_frame_in_parent_link.apply(frame.t + frame.R @ jpos))
-            joints.append(RawJoint(name=jname, kind=kind, parent=parent_name, child=name, origin=origin, axis=axis,
-                                   lower=rng[0], upper=rng[1], has_limits=limited and rng[1] > rng[0],
-                                   effort=gear * ctrl if ctrl > 0 else 0.0, velocity=0.0,
-                                   damping=float(je.get("damping", djoint.get("damping", 0.0))),
-                                   friction=float(je.get("frictionloss", djoint.get("frictionloss", 0.0))),
-                                   armature=float(je.get("armature", djoint.get("armature", 0.0))),
-                                   motor_gear=gear))
-            if np.any(jpos):  # move the link's content so its frame is the joint frame
+        if parent_name is not None and not jels:
+            # a body without a joint is welded to its parent: a fixed child, reported as a link of its own
+            joints.append(RawJoint(name=f"{name}_fixed", kind=JOINT_FIXED, parent=parent_name, child=name,
+                                   origin=parent_frame_in_parent_link.compose(frame), axis=np.array([1.0, 0.0, 0.0])))
+            child_frame = Pose()
+        elif parent_name is not None:
+            # MuJoCo applies a body's joints in document order, each about its own pos: joints 1..k-1 hang hidden
+            # links (no mass, no shapes; frames parallel to the body's at q = 0) between the parent and the body,
+            # which itself hangs on joint k
+            link_parent, prev_pos = parent_name, None
+            for k, je in enumerate(jels):
+                ja = attrs(je, childclass) if je.tag == "joint" else {"type": "free"}
+                jtype = ja.get("type", "hinge")
+                kind = {"hinge": JOINT_REVOLUTE, "slide": JOINT_PRISMATIC}.get(jtype)
+                if kind is None:
+                    raise ValueError(f"{path}: joint type {jtype} on a non-root body is not supported")
+                axis = np.array(_vec(ja.get("axis"), 3, [0, 0, 1]), dtype=np.float64)
+                axis /= np.linalg.norm(axis)
+                jpos = np.array(_vec(ja.get("pos"), 3, [0, 0, 0]), dtype=np.float64)
+                limited = ja.get("limited", "false") == "true"
+                rng = _vec(ja.get("range"), 2, [0.0, 0.0])
+                if kind == JOINT_REVOLUTE and degrees:
+                    rng = [math.radians(v) for v in rng]
+                jname = ja.get("name") or f"joint{len(joints)}"
+                gear, ctrl = gears.get(jname, (0.0, 0.0))
+                if prev_pos is None:
+                    # joint frame: body frame shifted by pos; the child link frame is re-expressed so that the
+                    # joint sits at its origin (geoms/inertia are moved by -pos below)
+                    origin = Pose(parent_frame_in_parent_link.R @ frame.R,
+                                  parent_frame_in_parent_link.apply(frame.t + frame.R @ jpos))
+                else:
+                    origin = Pose(np.eye(3), jpos - prev_pos)
+                last = k == len(jels) - 1
+                child = name if last else f"{name}/{jname}"
+                if not last:
+                    links[child] = RawLink(child, None, [], hidden=True)
+                    order.insert(order.index(name), child)
+                joints.append(RawJoint(name=jname, kind=kind, parent=link_parent, child=child, origin=origin, axis=axis,
+                                       lower=rng[0], upper=rng[1], has_limits=limited and rng[1] > rng[0],
+                                       effort=gear * ctrl if ctrl > 0 else 0.0, velocity=0.0,
+                                       damping=float(ja.get("damping", 0.0)),
+                                       friction=float(ja.get("frictionloss", 0.0)),
+                                       armature=float(ja.get("armature", 0.0)),
+                                       motor_gear=gear, stiffness=float(ja.get("stiffness", 0.0))))
+                link_parent, prev_pos = child, jpos
+            if np.any(jpos):  # move the link's content so its frame is the (last) joint's frame
                 sh = Pose(np.eye(3), -jpos)
                 link = links[name]
                 link.shapes = [RawShape(s.kind, sh.compose(s.pose), s.size) for s in link.shapes]
@@ -226,13 +253,70 @@ def parse_mjcf(path: str) -> RawModel:
                 raise ValueError(f"{path}: the root body must be free (or have no joint)")
             child_frame = Pose()
         for cb in be.findall("body"):
-            visit(cb, name, child_frame)
+            visit(cb, name, child_frame, childclass)
 
     wb = root.find("worldbody")
     tops = wb.findall("body")
     if len(tops) != 1:
         raise ValueError(f"{path}: expected one top-level body, found {len(tops)}")
-    visit(tops[0], None, Pose())
-    # default shape friction (MuJoCo geom friction[0]) for the asset's rigid shape properties
-    return RawModel(root.get("model", "mjcf"), links, order, joints,
-                    float(dgeom.get("friction", "1 0.005 0.0001").split()[0]))
+    visit(tops[0], None, Pose(), None)
+    # default shape friction (MuJoCo geom friction[0]) for the asset's rigid shape properties: the root body's class
+    root_cls = tops[0].get("childclass") or MAIN_CLASS
+    friction = classes.get(root_cls, {}).get("geom", {}).get("friction", "1 0.005 0.0001")
+    model = RawModel(root.get("model", "mjcf"), links, order, joints, float(friction.split()[0]))
+    # URDF-style loading sorts siblings by name; MJCF keeps document order.  Recorded only where the two differ
+    # (nv_ant.xml: they coincide)
+    model.document_order = _sorted_order(model) != order
+    # get_asset_actuator_properties lists the motors' efforts in <actuator> order; recorded only where the listed value
+    # (gear x control limit, or the gear of a motor without a control limit) in that order differs from the same in
+    # DOF order (nv_ant.xml: every motor is 15)
+    by_name = {j.name: j for j in joints}
+    dof_order = [j.name for j in joints if j.name in gears]
+
+    def listed(n):
+        g, ctrl = gears[n]
+        return g * ctrl if ctrl > 0 else g
+    if [listed(n) for n in motors] != [listed(n) for n in dof_order]:
+        model.actuator_order = list(motors)
+    return model
+
+
+MAIN_CLASS = "main"  # MuJoCo's name for the unnamed top-level default
+
+
+def _default_classes(root) -> Dict[str, Dict[str, Dict[str, str]]]:
+    """class name -> element tag -> attributes, from the ``<default>`` tree: a nested class starts from its
+    parent's settings and overrides them; the unnamed top-level default is MAIN_CLASS."""
+    classes: Dict[str, Dict[str, Dict[str, str]]] = {MAIN_CLASS: {}}
+
+    def walk(de, inherited, top: bool):
+        own = {tag: dict(a) for tag, a in inherited.items()}
+        for el in de:
+            if el.tag != "default":
+                own[el.tag] = {**own.get(el.tag, {}), **el.attrib}
+        name = de.get("class") or (MAIN_CLASS if top else None)
+        if name is None:
+            raise ValueError("a nested <default> needs a class name")
+        classes[name] = own
+        for sub in de.findall("default"):
+            walk(sub, own, False)
+
+    for de in root.findall("default"):
+        walk(de, classes[MAIN_CLASS], True)
+    return classes
+
+
+def _sorted_order(model: RawModel) -> List[str]:
+    """Depth-first link order with siblings sorted by name (build_articulation's order for a URDF)."""
+    kids: Dict[str, List[str]] = {}
+    for j in model.joints:
+        kids.setdefault(j.parent, []).append(j.child)
+    out: List[str] = []
+
+    def walk(n):
+        out.append(n)
+        for c in sorted(kids.get(n, [])):
+            walk(c)
+
+    walk(model.link_order[0])
+    return out

@@ -257,6 +257,7 @@ class Asset:
             p[i]["effort"] = d.effort
             p[i]["friction"] = d.friction
             p[i]["damping"] = d.damping
+            p[i]["stiffness"] = d.stiffness  # (MJCF joint stiffness; acts in DOF_MODE_POS only)
             p[i]["armature"] = self.options.armature if d.armature is None else d.armature
         return p
 
@@ -398,7 +399,7 @@ class Sim:
         # (GS_SELF_COLLIDE=0 turns the pairs off: an A/B knob for measurements, not a product setting)
         self.self_collide = bool(filters.pop()) and int(flat["npair"]) > 0 and os.environ.get("GS_SELF_COLLIDE", "1") != "0"
         _lib.check(L.gs_sim_set_self_collision(self.handle, int(self.self_collide)), "gs_sim_set_self_collision")
-        sens = [b for b, _ in self.asset.sensors]
+        sens = [self._sensor_body(b) for b, _ in self.asset.sensors]
         if sens:
             sb = np.ascontiguousarray(sens, dtype=np.int32)
             _lib.check(L.gs_sim_set_force_sensors(self.handle, len(sens), sb.ctypes.data), "gs_sim_set_force_sensors")
@@ -457,6 +458,17 @@ class Sim:
         self.refresh("contact")
         for kind in ("rigid_body", "jacobian", "mass_matrix"):  # acquired before prepare_sim
             self.refresh(kind)
+
+    def _sensor_body(self, link: int) -> int:
+        """The dynamic body of a force sensor's rigid body (create_asset_force_sensor takes a reported index)."""
+        art = self.asset.art
+        if art.links is None:
+            return link
+        l = art.links[link]
+        if not (np.allclose(l.pose.R, np.eye(3)) and np.allclose(l.pose.t, 0.0)):
+            raise NotImplementedError(f"force sensor on {l.name}: a link welded into another body has no joint "
+                                      f"reaction of its own (DESIGN.md section 6)")
+        return l.body
 
     def _effective_dof_props(self, p):
         """(kp, kd, effort, lower, upper, velocity) float64 [nd] of one actor's dof properties as the solver reads
@@ -759,7 +771,7 @@ class Gym:
         return asset.art.num_dofs
 
     def get_asset_rigid_body_count(self, asset: Asset) -> int:
-        return asset.art.num_links
+        return asset.art.num_public_links
 
     def get_asset_rigid_shape_count(self, asset: Asset) -> int:
         return asset.art.num_shapes
@@ -801,7 +813,14 @@ class Gym:
 
     def get_asset_actuator_properties(self, asset: Asset):
         # MJCF motors carry their gear (ant.py:160-162 reads it as motor_effort); URDF: the effort limit
-        return [ActuatorProperties(d.motor_gear if d.motor_gear > 0 else d.effort) for d in asset.art.dofs]
+        # (gear x control limit where the motor's control is limited, nv_humanoid.xml).  The motors come in the
+        # file's <actuator> order where the asset records one: humanoid.py:160-163 multiplies actions in DOF order
+        # by this list as it is
+        dofs = asset.art.dofs
+        if asset.art.actuator_dofs is not None:
+            dofs = [dofs[i] for i in asset.art.actuator_dofs]
+        return [ActuatorProperties(d.effort if d.motor_gear > 0 and d.effort > 0 else
+                                   d.motor_gear if d.motor_gear > 0 else d.effort) for d in dofs]
 
     def get_asset_actuator_count(self, asset: Asset) -> int:
         return asset.art.num_dofs
@@ -890,7 +909,7 @@ class Gym:
         return env.actors[actor].asset.art.num_dofs
 
     def get_actor_rigid_body_count(self, env: Env, actor: int) -> int:
-        return env.actors[actor].asset.art.num_links
+        return env.actors[actor].asset.art.num_public_links
 
     def get_actor_rigid_body_names(self, env: Env, actor: int):
         return env.actors[actor].asset.art.link_names()
@@ -923,12 +942,22 @@ class Gym:
         sim._tensors()
         return GymTensor(sim.dof_tensor, "dof")
 
+    @staticmethod
+    def _refuse_hidden_links(sim: Sim, what: str):
+        art = sim.asset.art if sim.asset is not None else None
+        if art is not None and art.num_hidden_links:
+            raise NotImplementedError(f"{what}: {art.name} has {art.num_hidden_links} hidden links (multi-joint MJCF "
+                                      f"bodies) after its {art.num_public_links} rigid bodies; the per-rigid-body "
+                                      f"tensors are not offered for such an asset (DESIGN.md section 6)")
+
     def acquire_net_contact_force_tensor(self, sim: Sim) -> GymTensor:
+        self._refuse_hidden_links(sim, "acquire_net_contact_force_tensor")
         sim._tensors()
         return GymTensor(sim.contact_tensor, "contact")
 
     def acquire_rigid_body_state_tensor(self, sim: Sim) -> GymTensor:
         """[num_envs * num_bodies, 13]: link origin, quat xyzw, COM linear velocity, angular velocity."""
+        self._refuse_hidden_links(sim, "acquire_rigid_body_state_tensor")
         return GymTensor(sim.kinematics_tensor("rigid_body"), "rigid_body")
 
     def acquire_force_sensor_tensor(self, sim: Sim) -> GymTensor:
@@ -945,6 +974,7 @@ class Gym:
         6, num_dofs] (the welded root row dropped, as Isaac Gym does).  Rows: COM linear velocity (3),
         angular velocity (3); columns: root link COM linear / angular velocity, dof velocities."""
         self._check_actor_name(sim, name)
+        self._refuse_hidden_links(sim, "acquire_jacobian_tensor")
         t = sim.kinematics_tensor("jacobian")
         return GymTensor(t[:, 1:] if sim.asset.art.fixed_base else t, "jacobian")
 

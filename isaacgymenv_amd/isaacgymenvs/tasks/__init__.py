@@ -4,6 +4,7 @@ from .anymal import Anymal, Hound
 from .anymal_terrain import AnymalTerrain
 from .cartpole import Cartpole
 from .hound_arm import Houndarm
+from .humanoid import Humanoid
 from .manipulator import Manipulator
 from .hound_terrain import HoundTerrain
 from .useful_hound import UsefulHound
@@ -16,6 +17,7 @@ isaacgym_task_map = {
     "Hound": Hound,
     "HoundTerrain": HoundTerrain,
     "Houndarm": Houndarm,
+    "Humanoid": Humanoid,
     "Manipulator": Manipulator,
     "UsefulHound": UsefulHound,
 }

@@ -129,3 +129,8 @@ def compute_rot(torso_quat, velocity, ang_velocity, targets, torso_positions):
     roll, pitch, yaw = get_euler_xyz(torso_quat)
     walk_target_angle = torch.atan2(targets[:, 2] - torso_positions[:, 2], targets[:, 0] - torso_positions[:, 0])
     return vel_loc, angvel_loc, roll, pitch, yaw, walk_target_angle - yaw
+
+
+def normalize_angle(x: torch.Tensor) -> torch.Tensor:
+    """The angle on (-pi, pi] (torch_jit_utils.py:126-128)."""
+    return torch.atan2(torch.sin(x), torch.cos(x))

@@ -34,6 +34,8 @@ GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 GOLDEN_SOURCES = {
     "open_manipulator_p.model.json": "urdf/open_manipulator_p_gazebo/urdf/open_manipulator_p.urdf",
     "franka_panda_manipulator.model.json": "urdf/franka_description/robots/franka_panda_manipulator.urdf",
+    # the Humanoid task's body (humanoid.py:143): multi-joint bodies as hidden links, nested default classes
+    "nv_humanoid.model.json": "mjcf/nv_humanoid.xml",
 }
 
 
