@@ -76,6 +76,19 @@ def _link_poses(f, root, q):
     return K.link_frames(f, R, p)
 
 
+def check_jacobian_against_fk(f, root, dof, eps=1e-6, atol=2e-7):
+    """Every Jacobian column of every link of the envs (root [n,13], dof [n,nd,2]) against central differences of FK."""
+    for e in range(root.shape[0]):
+        _, jac, _ = K.env_kinematics(f, root[e], dof[e])
+        nv = jac.shape[2]
+        for k in range(nv):
+            rp, qp = _perturbed(f, root[e], dof[e, :, 0], k, eps)
+            rm, qm = _perturbed(f, root[e], dof[e, :, 0], k, -eps)
+            for l, ((_, Rp, _, xp), (_, Rm, _, xm)) in enumerate(zip(_link_poses(f, rp, qp), _link_poses(f, rm, qm))):
+                np.testing.assert_allclose(jac[l, 0:3, k], (xp - xm) / (2 * eps), atol=atol)
+                np.testing.assert_allclose(jac[l, 3:6, k], _rotvec(Rp @ Rm.T) / (2 * eps), atol=atol)
+
+
 @pytest.mark.parametrize("kind", ["hound", "anymal", "cartpole"])
 def test_jacobian_matches_fk_finite_differences(kind):
     art, f = getattr(H, kind)()
@@ -86,40 +99,32 @@ def test_jacobian_matches_fk_finite_differences(kind):
     else:
         root = np.zeros((3, 13)); root[:, 6] = 1.0
         dof = np.random.RandomState(4).uniform(-1, 1, (3, 2, 2))
-    eps = 1e-6
-    for e in range(3):
-        _, jac, _ = K.env_kinematics(f, root[e], dof[e])
-        nv = jac.shape[2]
-        for k in range(nv):
-            rp, qp = _perturbed(f, root[e], dof[e, :, 0], k, eps)
-            rm, qm = _perturbed(f, root[e], dof[e, :, 0], k, -eps)
-            for l, ((_, Rp, _, xp), (_, Rm, _, xm)) in enumerate(zip(_link_poses(f, rp, qp), _link_poses(f, rm, qm))):
-                np.testing.assert_allclose(jac[l, 0:3, k], (xp - xm) / (2 * eps), atol=2e-7)
-                np.testing.assert_allclose(jac[l, 3:6, k], _rotvec(Rp @ Rm.T) / (2 * eps), atol=2e-7)
+    check_jacobian_against_fk(f, root, dof)
 
 
-@pytest.mark.parametrize("kind", ["hound", "anymal"])
-def test_mass_matrix_is_the_kinetic_energy_metric(kind):
-    """1/2 nu^T M nu == sum_b 1/2 m_b |v_b|^2 + 1/2 w_b^T I_b w_b, body velocities by finite
-    differences of FK along nu (independent of the Jacobian code)."""
-    art, f = getattr(H, kind)()
-    root, dof, _, _ = getattr(H, f"{kind}_states")(4, seed=9)
-    eps = 1e-6
-    for e in range(4):
+def check_mass_matrix_is_kinetic_energy_metric(f, root, dof, eps=1e-6, rtol=1e-6):
+    """For every env: M symmetric and positive definite, and 1/2 nu^T M nu == sum_b 1/2 m_b |v_b|^2 + 1/2 w_b^T I_b w_b
+    with the body velocities by finite differences of FK along nu (independent of the Jacobian code).  Returns the
+    smallest eigenvalue met."""
+    nbase = 0 if f["fixed_base"] else 6
+    low = np.inf
+    for e in range(root.shape[0]):
         R, p, _, _ = K.fk(f, root[e], dof[e, :, 0])
         nu = K.generalized_velocity(f, root[e], dof[e], R, p)
         _, _, M = K.env_kinematics(f, root[e], dof[e])
         np.testing.assert_allclose(M, M.T, atol=1e-12)
-        assert np.linalg.eigvalsh(M).min() > 0
+        low = min(low, np.linalg.eigvalsh(M).min())
+        assert low > 0
 
         def pose(sign):
-            r, q = root[e].copy(), dof[e, :, 0] + sign * eps * nu[6:]
-            R0 = K.quat_to_mat(r[3:7])
-            c = r[0:3] + R0 @ f["lcom"][0]
-            Rd = K.rodrigues(nu[3:6] / max(np.linalg.norm(nu[3:6]), 1e-300), sign * eps * np.linalg.norm(nu[3:6]))
-            c2 = c + sign * eps * nu[0:3]
-            r[0:3] = c2 + Rd @ (r[0:3] - c)
-            r[3:7] = K.mat_to_quat(Rd @ R0)
+            r, q = root[e].copy(), dof[e, :, 0] + sign * eps * nu[nbase:]
+            if nbase:
+                R0 = K.quat_to_mat(r[3:7])
+                c = r[0:3] + R0 @ f["lcom"][0]
+                Rd = K.rodrigues(nu[3:6] / max(np.linalg.norm(nu[3:6]), 1e-300), sign * eps * np.linalg.norm(nu[3:6]))
+                c2 = c + sign * eps * nu[0:3]
+                r[0:3] = c2 + Rd @ (r[0:3] - c)
+                r[3:7] = K.mat_to_quat(Rd @ R0)
             return K.fk(f, r, q)
 
         Rp, pp, _, _ = pose(1)
@@ -132,7 +137,15 @@ def test_mass_matrix_is_the_kinetic_energy_metric(kind):
             w = _rotvec(Rp[b] @ Rm[b].T) / (2 * eps)
             Iw = R[b] @ f["inertia"][b].reshape(3, 3) @ R[b].T
             ke += 0.5 * f["mass"][b] * v @ v + 0.5 * w @ Iw @ w
-        np.testing.assert_allclose(0.5 * nu @ M @ nu, ke, rtol=1e-6)
+        np.testing.assert_allclose(0.5 * nu @ M @ nu, ke, rtol=rtol)
+    return low
+
+
+@pytest.mark.parametrize("kind", ["hound", "anymal"])
+def test_mass_matrix_is_the_kinetic_energy_metric(kind):
+    art, f = getattr(H, kind)()
+    root, dof, _, _ = getattr(H, f"{kind}_states")(4, seed=9)
+    check_mass_matrix_is_kinetic_energy_metric(f, root, dof)
 
 
 def test_rigid_body_velocities_are_jacobian_times_nu():
