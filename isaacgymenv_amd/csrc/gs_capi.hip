@@ -245,7 +245,7 @@ int gs_sim_add_triangle_mesh(gs_sim* s, const float* vertices, int64_t num_verti
   (void)restitution;
   if (!s || !vertices || !triangles) return fail("gs_sim_add_triangle_mesh: null argument");
   if (s->topo) return fail("gs_sim_add_triangle_mesh: call before the model is set (prepare_sim)");
-  if (s->d_terr[0]) return fail("gs_sim_add_triangle_mesh: one triangle mesh per sim");
+  if (s->dp.has_terrain) return fail("gs_sim_add_triangle_mesh: one triangle mesh per sim");
   TerrainTables tt;
   if (terrain_build(vertices, num_vertices, triangles, num_triangles, transform_p, &tt))
     return fail("%s", tt.err.c_str());

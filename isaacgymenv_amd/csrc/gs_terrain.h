@@ -11,7 +11,8 @@
 //   triangle whose closest point q to c lies within thr, and whose face normal is not pointing down
 //   (n_z >= TERRAIN_DOWN_NZ), is a candidate surface:
 //     * q interior to the face: normal = the face normal nf, separation = nf.(c - a) - r, also
-//       when the centre is below the face by at most r + TERRAIN_BACK (penetration);
+//       when the centre is below the face by at most r + TERRAIN_BACK (penetration; then also when the centre's
+//       projection falls on the face's rim within rounding, on_rim);
 //     * q on an edge or vertex: only from the front side (nf.(c - a) >= 0), normal = (c - q)/|c - q|,
 //       separation = |c - q| - r;
 //   the candidate keeps the surface of the triangle CLOSEST to its centre (|sd| for a face, |c - q|
@@ -19,7 +20,7 @@
 //   (i, j) order, the two triangles of a cell in the order above (a foot pushed into a stair riser
 //   below the tread's edge is pushed back out of the riser, not lifted onto the tread, unless the
 //   tread is nearer).
-// Cells are culled by their top height (a centre more than thr above every vertex of a cell
+// Cells are culled by their top height (a centre more than low_reach() above every vertex of a cell
 // cannot touch it from the front nor lie behind one of its faces), by their (move-extended)
 // footprint widened by the horizontal reach max(thr, r + TERRAIN_BACK), and -- once a surface is
 // found -- by their bounding box: a triangle's key is its distance to the centre, at least the box's,
@@ -39,6 +40,9 @@
 // would otherwise admit a sphere centre lying inside the terrain and push it down along the
 // inverted normal (trimesh AnymalTerrain blow-up, tools/probes/trimesh_nan_replay.py)
 #define TERRAIN_DOWN_NZ (-0.5f)
+// a projection within this multiple of (|x| + |y| + |z| + 1) of a face's rim counts as on the face for a centre
+// behind it (on_rim): 2^-22, two roundings of the coordinates
+#define TERRAIN_RIM 2.4e-7f
 
 struct TerrainDev {
   const float4* v;     // [rows*cols] world xyz (transform applied), w unused
@@ -127,6 +131,17 @@ GS_HD bool closest_on_triangle(const float* p, const float* a, const float* b, c
   return true;
 }
 
+// A centre behind a face (sd < 0) whose closest point q lies on the face's rim: true when the centre's projection
+// onto the face's plane is q itself within the rounding of the coordinates (TERRAIN_RIM).  Such a centre is under an
+// edge or vertex of the face, not beside it, and keeps the face's contact: each of the coplanar faces that share a
+// grid line may call a projection on that line outside (exactly on it they all do), and a penetrating sphere
+// exactly over the line would find no surface at all.
+GS_HD bool on_rim(const float* p, const float* q, const float* nf, float sd) {
+  const float o[3] = {p[0] - q[0] - sd * nf[0], p[1] - q[1] - sd * nf[1], p[2] - q[2] - sd * nf[2]};
+  const float rim = TERRAIN_RIM * (fabsf(p[0]) + fabsf(p[1]) + fabsf(p[2]) + 1.f);
+  return dot3(o, o) <= rim * rim;
+}
+
 // one triangle: update (bkey, best, n) when it is an admissible surface closer to the centre
 GS_HD void triangle(const float* p, float r, float thr, const float4& A, const float4& B,
                                          const float4& C, float& bkey, float& best, float* n) {
@@ -149,7 +164,10 @@ GS_HD void triangle(const float* p, float r, float thr, const float4& A, const f
     if (key < bkey) { bkey = key; best = sd - r; n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2]; }
     return;
   }
-  if (sd < 0.f) return;
+  if (sd < 0.f) {
+    if (on_rim(p, q, nf, sd) && -sd < bkey) { bkey = -sd; best = sd - r; n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2]; }
+    return;
+  }
   const float d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
   const float dd = dot3(d, d);
   if (dd > thr * thr) return;
@@ -181,7 +199,10 @@ GS_HD void triangle_n(const float* p, float r, float thr, const float4& A, const
     if (key < bkey) { bkey = key; best = sd - r; n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2]; }
     return;
   }
-  if (sd < 0.f) return;
+  if (sd < 0.f) {
+    if (on_rim(p, q, nf, sd) && -sd < bkey) { bkey = -sd; best = sd - r; n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2]; }
+    return;
+  }
   const float d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
   const float dd = dot3(d, d);
   if (dd > thr * thr) return;
@@ -198,6 +219,11 @@ GS_HD void triangle_n(const float* p, float r, float thr, const float4& A, const
   }
 }
 
+// How far below its centre a sphere can meet a cell: thr from the front; from behind a face the centre lies up to
+// r + TERRAIN_BACK along the normal, which an overhanging face (n_z down to TERRAIN_DOWN_NZ) turns into a height of
+// up to -TERRAIN_DOWN_NZ (r + TERRAIN_BACK) ABOVE the face's top (for radii below 0.06 m the larger of the two).
+GS_HD float low_reach(float r, float thr) { return fmaxf(thr, -TERRAIN_DOWN_NZ * (r + TERRAIN_BACK)); }
+
 // false when no cell around sphere (p, r) can hold a surface within thr: the range of cells within the horizontal
 // reach is empty, or the sphere's lowest reach lies above the highest cell top of the range (from the 4 x 4
 // square maxima; ranges wider than 8 cells from the 8 x 8 block summary).  sphere_contact starts with exactly this test; the lane team runs it alone first to hand only
@@ -208,7 +234,7 @@ GS_HD bool may_contact(const TerrainDev& T, const float* p, float r, float thr) 
   const int i0 = gs_imax((int)floorf(gx - gt) - 1, 0), i1 = gs_imin((int)floorf(gx + gt) + 1, T.rows - 2);
   const int j0 = gs_imax((int)floorf(gy - gt) - 1, 0), j1 = gs_imin((int)floorf(gy + gt) + 1, T.cols - 2);
   if (i0 > i1 || j0 > j1) return false;
-  const float zlo = p[2] - thr;
+  const float zlo = p[2] - low_reach(r, thr);
   if (i1 - i0 <= 7 && j1 - j0 <= 7) {
     // the range's highest top exactly-or-above from four overlapping 4 x 4 squares (their union covers a range
     // up to 8 cells wide; a narrower, clipped range is covered with room to spare): one batch of loads
@@ -249,7 +275,7 @@ GS_HD bool sphere_contact_scan(const TerrainDev& T, const float* p, float r, flo
   const int i0 = gs_imax((int)floorf(gx - gt) - 1, 0), i1 = gs_imin((int)floorf(gx + gt) + 1, T.rows - 2);
   const int j0 = gs_imax((int)floorf(gy - gt) - 1, 0), j1 = gs_imin((int)floorf(gy + gt) + 1, T.cols - 2);
   float best = 3.0e38f, bkey = 3.0e38f;
-  const float zlo = p[2] - thr;
+  const float zlo = p[2] - low_reach(r, thr);
   const float pad = 1e-4f * T.hs;
   // one cell given its info word: the culling tests, then its two triangles (vertices loaded here unless given:
   // the cell record's TERRAIN_REC float4 with GS_TERR_PLANES, else the four vertices)

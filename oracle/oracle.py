@@ -69,6 +69,8 @@ def _lib(real_bits: int):
             [C.c_double if real_bits == 64 else C.c_float, C.c_void_p]
         lib.oracle_terrain_query.restype = C.c_int
         lib.oracle_terrain_query.argtypes = [C.POINTER(OParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.oracle_terrain_query_kind.restype = C.c_int
+        lib.oracle_terrain_query_kind.argtypes = [C.POINTER(OParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIBS[real_bits] = lib
     return _LIBS[real_bits]
 
@@ -154,6 +156,18 @@ class OracleSim:
         if self.lib.oracle_terrain_query(C.byref(self.params), c.shape[0], c.ctypes.data, r.ctypes.data,
                                          out.ctypes.data) != 0:
             raise RuntimeError("oracle_terrain_query: no terrain")
+        return out
+
+    def terrain_query_kind(self, centres, radii):
+        """terrain_query with the winning surface's kind and margin: [n][7] = (found, separation, normal xyz, kind,
+        margin), kind 1 a face from the front, 2 a face from behind, 3 an edge or vertex, 0 nothing found; margin
+        how much nearer the winner is than the nearest surface that would give another answer."""
+        c = np.ascontiguousarray(centres, dtype=self.real)
+        r = np.ascontiguousarray(radii, dtype=self.real)
+        out = np.zeros((c.shape[0], 7), dtype=self.real)
+        if self.lib.oracle_terrain_query_kind(C.byref(self.params), c.shape[0], c.ctypes.data, r.ctypes.data,
+                                              out.ctypes.data) != 0:
+            raise RuntimeError("oracle_terrain_query_kind: no terrain")
         return out
 
     def hull_select(self, shape: int, R, P, rootz: float):

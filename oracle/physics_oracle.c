@@ -188,7 +188,7 @@ static void seg_closest(const real *p, const real *a, const real *b, real *q) {
 /* candidate surface of one triangle: key = distance from the centre to the triangle (the closest
  * surface wins), separation signed (negative behind a face) */
 static void tri_test(const real *p, real r, real thr, const real *a, const real *b, const real *c, real *bkey,
-                     real *bsep, real *n) {
+                     real *bsep, real *n, int *kind) {
     real e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]}, nf[3];
     cross3(e1, e2, nf);
     const real l = sqrt(dot3(nf, nf));
@@ -206,7 +206,10 @@ static void tri_test(const real *p, real r, real thr, const real *a, const real 
     const real bv = (d11 * d20 - d01 * d21) / den, bw = (d00 * d21 - d01 * d20) / den;
     if (bv >= 0 && bw >= 0 && bv + bw <= 1) {
         const real key = fabs(sd);
-        if (key < *bkey) { *bkey = key; *bsep = sd - r; n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2]; }
+        if (key < *bkey) {
+            *bkey = key; *bsep = sd - r; n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2];
+            if (kind) *kind = sd < 0 ? 2 : 1;
+        }
         return;
     }
     if (sd < 0) return;
@@ -224,9 +227,12 @@ static void tri_test(const real *p, real r, real thr, const real *a, const real 
         *bsep = dist - r;
         if (dist > 1e-7) { for (int k = 0; k < 3; ++k) n[k] = (p[k] - q[k]) / dist; }
         else { n[0] = nf[0]; n[1] = nf[1]; n[2] = nf[2]; }
+        if (kind) *kind = 3;
     }
 }
-static int terrain_query(const OParams *pp, const real *p, real r, real thr, real *sep, real *n) {
+/* kind (may be NULL): the winning surface's kind, 1 a face from the front, 2 a face from behind (sd < 0),
+ * 3 an edge or vertex */
+static int terrain_query_kind(const OParams *pp, const real *p, real r, real thr, real *sep, real *n, int *kind) {
     const real hs = (real)pp->ths;
     const int gi = (int)floor((p[0] - (real)pp->tx0) / hs), gj = (int)floor((p[1] - (real)pp->ty0) / hs);
     const real reach = thr > r + TERRAIN_BACK ? thr : r + TERRAIN_BACK;
@@ -244,13 +250,49 @@ static int terrain_query(const OParams *pp, const real *p, real r, real thr, rea
                                    (int64_t)(i + 1) * pp->tcols + j, (int64_t)(i + 1) * pp->tcols + j + 1};
             for (int k = 0; k < 4; ++k)
                 for (int a = 0; a < 3; ++a) v[k][a] = (real)pp->tverts[3 * id[k] + a];
-            tri_test(p, r, thr, v[0], v[3], v[1], &bkey, &best, n);
-            tri_test(p, r, thr, v[0], v[2], v[3], &bkey, &best, n);
+            tri_test(p, r, thr, v[0], v[3], v[1], &bkey, &best, n, kind);
+            tri_test(p, r, thr, v[0], v[2], v[3], &bkey, &best, n, kind);
         }
     }
     if (!(best < thr - r)) return 0;
     *sep = best;
     return 1;
+}
+/* How far the winner's key lies below the nearest candidate surface that would give another answer (a separation
+ * more than 1e-4 or a normal component more than 0.1 away; the contact of a face and the edge contact of its rim
+ * next to it differ by less and run into each other): 1e300 when there is none.  Two surfaces can tie
+ * exactly, under every perturbation of the centre: a cell folded onto itself by the slope correction is two
+ * coincident faces with opposite normals. */
+static real terrain_margin(const OParams *pp, const real *p, real r, real thr, real sep, const real *n) {
+    const real hs = (real)pp->ths;
+    const int gi = (int)floor((p[0] - (real)pp->tx0) / hs), gj = (int)floor((p[1] - (real)pp->ty0) / hs);
+    const real reach = thr > r + TERRAIN_BACK ? thr : r + TERRAIN_BACK;
+    const int w = (int)ceil(reach / hs) + 3;
+    real wkey = 1e300, other = 1e300;
+    for (int i = gi - w; i <= gi + w; ++i) {
+        if (i < 0 || i > pp->trows - 2) continue;
+        for (int j = gj - w; j <= gj + w; ++j) {
+            if (j < 0 || j > pp->tcols - 2) continue;
+            real v[4][3];
+            const int64_t id[4] = {(int64_t)i * pp->tcols + j, (int64_t)i * pp->tcols + j + 1,
+                                   (int64_t)(i + 1) * pp->tcols + j, (int64_t)(i + 1) * pp->tcols + j + 1};
+            for (int k = 0; k < 4; ++k)
+                for (int a = 0; a < 3; ++a) v[k][a] = (real)pp->tverts[3 * id[k] + a];
+            for (int t = 0; t < 2; ++t) {
+                real key = 1e300, s = 1e300, nn[3] = {0, 0, 0};
+                tri_test(p, r, thr, v[0], t ? v[2] : v[3], t ? v[3] : v[1], &key, &s, nn, NULL);
+                if (!(key < 1e300)) continue;
+                const int same = fabs(s - sep) <= 1e-4 && fabs(nn[0] - n[0]) <= 0.1 && fabs(nn[1] - n[1]) <= 0.1 &&
+                                 fabs(nn[2] - n[2]) <= 0.1;
+                if (same) { if (key < wkey) wkey = key; }
+                else if (key < other) other = key;
+            }
+        }
+    }
+    return other < 1e300 ? other - wkey : 1e300;
+}
+static int terrain_query(const OParams *pp, const real *p, real r, real thr, real *sep, real *n) {
+    return terrain_query_kind(pp, p, r, thr, sep, n, NULL);
 }
 /* contact frame tangents: world x projected on the contact plane (world y when n ~ x), t2 = n x t1 */
 static void tangents(const real *n, real *t1, real *t2) {
@@ -1427,10 +1469,30 @@ int oracle_real_size(void) { return (int)sizeof(real); }
 /* the terrain contact query alone (test hook): out[n][5] = (found, separation, normal xyz) */
 int oracle_terrain_query(const OParams *p, int n, const real *centres, const real *radii, real *out) {
     if (!p->has_terrain) return -1;
+#pragma omp parallel for schedule(static)
     for (int t = 0; t < n; ++t) {
         real sep = 0, nn[3] = {0, 0, 0};
         const int f = terrain_query(p, centres + 3 * t, radii[t], radii[t] + (real)p->contact_offset, &sep, nn);
         out[5 * t] = f; out[5 * t + 1] = sep; out[5 * t + 2] = nn[0]; out[5 * t + 3] = nn[1]; out[5 * t + 4] = nn[2];
+    }
+    return 0;
+}
+
+/* the same with the winning surface's kind (terrain_query_kind; 0 when nothing is found) and its margin over the
+ * nearest surface with another answer (terrain_margin; 1e300 when nothing is found): out[n][7] =
+ * (found, separation, normal xyz, kind, margin) */
+int oracle_terrain_query_kind(const OParams *p, int n, const real *centres, const real *radii, real *out) {
+    if (!p->has_terrain) return -1;
+#pragma omp parallel for schedule(static)
+    for (int t = 0; t < n; ++t) {
+        real sep = 0, nn[3] = {0, 0, 0};
+        int kind = 0;
+        const int f = terrain_query_kind(p, centres + 3 * t, radii[t], radii[t] + (real)p->contact_offset, &sep, nn,
+                                         &kind);
+        real *o = out + 7 * t;
+        o[0] = f; o[1] = sep; o[2] = nn[0]; o[3] = nn[1]; o[4] = nn[2];
+        o[5] = f ? kind : 0;
+        o[6] = f ? terrain_margin(p, centres + 3 * t, radii[t], radii[t] + (real)p->contact_offset, sep, nn) : 1e300;
     }
     return 0;
 }

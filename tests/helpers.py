@@ -343,6 +343,11 @@ def mesh_terrain(v, t, rows, cols, hs, shift=(0.0, 0.0, 0.0), friction=1.0):
 
 def rough_terrain(seed=0, rows=120, cols=120):
     """Stairs, blocks and a random field around the origin (cells of 0.1 m), centred on (0, 0)."""
+    return terrain_from_heights(rough_heights(seed, rows, cols), shift=(-rows * 0.05, -cols * 0.05, 0.0))
+
+
+def rough_heights(seed=0, rows=120, cols=120):
+    """rough_terrain's height samples (int16 counts of 0.005 m)."""
     from isaacgymenv_amd.isaacgym import terrain_utils as tu
     np.random.seed(seed)
     hf = np.zeros((rows, cols), dtype=np.int16)
@@ -353,7 +358,7 @@ def rough_terrain(seed=0, rows=120, cols=120):
     tu.discrete_obstacles_terrain(b, 0.1, 0.5, 1.0, 10, platform_size=0.5)
     hf[: rows // 2] = a.height_field_raw
     hf[rows // 2:] = b.height_field_raw
-    return terrain_from_heights(hf, shift=(-rows * 0.05, -cols * 0.05, 0.0))
+    return hf
 
 
 # per-field tolerances of one simulate (test_physics_gpu.py bounds) for assert_close_or_explained
